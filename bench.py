@@ -1,7 +1,12 @@
 """Benchmark: pdgstrf fp64 GFLOP/s + factor time, 3D 7-point Laplacian n = 1M.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 100]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 100] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: front-end,
+plan, upload, W warm-up steps, K timed steps, the result line.  --full adds
+every other measurement and check (below); --dump-outputs DIR writes the
+factors the last timed step computed (dump_outputs).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N
 ranks itself (spawn_ranks); a WORLD_SIZE that differs from --gpus, fewer
@@ -18,10 +23,12 @@ Each step is bracketed by a barrier + device synchronize; the reported time is
 the max over ranks.  value = algorithmic flops of the whole factorization
 (all ranks) / time.
 
-Extra fields: roofline of the dominant kernel (k_schur, fp64 MFMA bound) from
-HIP events recorded on the engine's stream during the timed steps, and the
-reference CPU pdgstrf (oracle/_ref, MPI + MKL) timed on a bounded sample on
-this host.
+Extra fields with --full: roofline of the dominant kernel (k_schur, fp64 MFMA
+bound) from HIP events recorded on the engine's stream in one extra serialized
+step, the device fill / solve / refine rows, the drop-in pdgstrf legs, the
+reference CPU pdgstrf (oracle/_ref, MPI + MKL) on the host's cores with the
+full-size parity check, and on a multi-rank grid the parity preflight.  Each
+has its own --no-* switch.
 """
 import argparse
 import json
@@ -303,6 +310,37 @@ def device_resident_leg(nx):
         return {"error": str(e)}
 
 
+DUMP_SAMPLE = 3_000_000  # values per array above which dump_outputs samples (2 x 24 MB in fp64)
+
+
+def dump_outputs(plan, lu, out_dir, keep_host):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step, the factors in the LUstruct's value arrays, as DIR/Lval.npy and
+    DIR/Uval.npy (this rank's; rank r > 0 of a grid writes Lval_rank<r>.npy).
+    plan.download() brings them from HBM into lu.Lval / lu.Uval.  An array
+    longer than DUMP_SAMPLE values is written as a fixed sample: the sorted
+    indices default_rng(0).integers(0, len, DUMP_SAMPLE), the same from run
+    to run, so two builds write the same entries.  Real types are written as
+    they are (float32 / float64), complex as (re, im) float64 pairs.
+    keep_host: put the host arrays' original values back afterwards (the legs
+    of --full factor them again)."""
+    saved = (lu.Lval.copy(), lu.Uval.copy()) if keep_host else None
+    plan.download()
+    os.makedirs(out_dir, exist_ok=True)
+    rank = int(os.environ.get("RANK", "0"))
+    for name, v in (("Lval", lu.Lval), ("Uval", lu.Uval)):
+        if len(v) > DUMP_SAMPLE:
+            v = v[np.sort(np.random.default_rng(0).integers(0, len(v), DUMP_SAMPLE))]
+        if np.iscomplexobj(v):
+            v = np.ascontiguousarray(v).view(np.float64).reshape(-1, 2)
+        f = name + (f"_rank{rank}" if rank else "") + ".npy"
+        np.save(os.path.join(out_dir, f), np.ascontiguousarray(v))
+        log(f"wrote {os.path.join(out_dir, f)}: {v.shape} {v.dtype}")
+    if saved:
+        lu.Lval[:] = saved[0]
+        lu.Uval[:] = saved[1]
+
+
 def one_norm(A):
     """||A||_1 (max column sum of |a_ij|), the anorm pdgssvx passes to pdgstrf."""
     colptr, _, val = A.arrays()
@@ -432,6 +470,14 @@ def main():
                     help="reference: pdgssvx's own sp_colorder + symbfact + pddistribute (the "
                          "LUstruct the reference hands pdgstrf for this perm_c; headline); "
                          "frontend: the library front-end's amalgamated supernodes")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the serialized roofline step, the fill / solve / "
+                         "refine rows, the drop-in pdgstrf legs, the reference CPU baseline with "
+                         "the full-size parity check and, on a grid, the parity preflight (each "
+                         "has its --no-* switch); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the factors of the last one as "
+                         "DIR/Lval.npy and DIR/Uval.npy (a fixed seeded sample of large arrays)")
     ap.add_argument("--cpu-ranks", type=int, default=16)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-next", action="store_true",
@@ -467,6 +513,11 @@ def main():
         return
     if args.workload != "lap3d":
         args.no_cpu = True  # the CPU baseline is the reference on the headline workload
+    if args.roofline_only:
+        args.full = True  # the serialized step is one of --full's
+    if not args.full:
+        args.no_cpu = args.no_next = args.no_abi = True
+        args.preflight_nx = 0
 
     # the library's exchange watchdog is opt-in: armed for the bench's ranks
     # (a hung exchange then ends with a diagnosis and exit 86, csrc/watchdog.h)
@@ -593,14 +644,19 @@ def main():
         st = plan.stats()
         for k in acc:
             acc[k] += st[k]
-    # kernel-level roofline: one more factorization with every launch on one
-    # stream, so k_schur_big launch durations are not stretched by the
-    # look-ahead kernels running beside them (not part of the timed steps)
-    plan.set_timing(2 if args.level_log else 1, serial=True)  # level log: serialized kernel times
-    one_step()
-    sst = plan.stats()
-    plan.set_timing(2 if args.level_log else 1, serial=False)
     st = plan.stats()
+    if args.dump_outputs:
+        dump_outputs(plan, lu, args.dump_outputs, keep_host=not args.no_abi)
+    sst = None
+    if args.full:
+        # kernel-level roofline: one more factorization with every launch on one
+        # stream, so k_schur_big launch durations are not stretched by the
+        # look-ahead kernels running beside them (not part of the timed steps)
+        plan.set_timing(2 if args.level_log else 1, serial=True)  # level log: serialized kernel times
+        one_step()
+        sst = plan.stats()
+        plan.set_timing(2 if args.level_log else 1, serial=False)
+        st = plan.stats()
     nxt = None
     if world == 1 and not args.no_next and not args.roofline_only:
         log("next rows (fill / solve / refine)")
@@ -668,22 +724,24 @@ def main():
             tn = "double" if dtype == 0 else "float"
             kname = f"k_schur_big<{tn}> (128x128 {W[7]} MFMA GEMM + fused scatter)"
             tkey = f"k_schur_big<{tn}>"
-        ker_ms, ker_flops = sst["t_schur_big_ms"], sst["schur_big_flops"]
-        launches = max(int(sst["n_schur_big_launches"]), 1)
-        achieved = ker_flops / (ker_ms / 1e3) / 1e12 if ker_ms > 0 else 0.0
-        roof = {"bound": "mfma", "achieved": round(achieved, 3),
-                "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4),
-                "traffic": pmc_traffic(args.workload, args.nx, pr, pc, tkey),
-                "kernel": kname,
-                "launches_per_step": launches,
-                "flops_per_launch": ker_flops / launches,
-                "avg_launch_ms": round(ker_ms / launches, 4),
-                "timer": "HIP events around each launch of the kernel, in one extra "
-                         "factorization with all launches on one stream (untimed for value)",
-                "serial_factor_ms": round(sst["t_total_ms"], 3),
-                "all_schur_tflops": round(st["schur_flops"] / (acc["t_schur_ms"] / 1e3 / K) / 1e12,
-                                          3) if acc["t_schur_ms"] else None}
+        roof = None  # the serialized step is one of --full's
+        if sst is not None:
+            ker_ms, ker_flops = sst["t_schur_big_ms"], sst["schur_big_flops"]
+            launches = max(int(sst["n_schur_big_launches"]), 1)
+            achieved = ker_flops / (ker_ms / 1e3) / 1e12 if ker_ms > 0 else 0.0
+            roof = {"bound": "mfma", "achieved": round(achieved, 3),
+                    "peak": peak, "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4),
+                    "traffic": pmc_traffic(args.workload, args.nx, pr, pc, tkey),
+                    "kernel": kname,
+                    "launches_per_step": launches,
+                    "flops_per_launch": ker_flops / launches,
+                    "avg_launch_ms": round(ker_ms / launches, 4),
+                    "timer": "HIP events around each launch of the kernel, in one extra "
+                             "factorization with all launches on one stream (untimed for value)",
+                    "serial_factor_ms": round(sst["t_total_ms"], 3),
+                    "all_schur_tflops": round(st["schur_flops"] / (acc["t_schur_ms"] / 1e3 / K) / 1e12,
+                                              3) if acc["t_schur_ms"] else None}
         cpu = parity = None
         if want_cpu:
             log(f"cpu baseline (reference pdgstrf, {args.nx}^3, {args.cpu_ranks} ranks)")

@@ -11,6 +11,6 @@ if [ -z "$SKIP_TESTS" ]; then
 fi
 for e in ${ENVS:-X=0}; do
   n=$(echo "$e" | tr '/=' '_-')
-  env $e timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu --no-next --no-abi --level-log > $O/bench_$n.json 2> $O/bench_$n.err || { tail -20 $O/bench_$n.err; exit 1; }
+  env $e timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --no-next --no-abi --level-log > $O/bench_$n.json 2> $O/bench_$n.err || { tail -20 $O/bench_$n.err; exit 1; }
   python -c "import json; d=json.load(open('$O/bench_$n.json')); print('$e', 'ms_per_step', d['ms_per_step'], 'frac', d['roofline']['frac'], 'serial', d['roofline']['serial_factor_ms'])"
 done

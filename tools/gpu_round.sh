@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \
     > $OUT/pytest_gpu.log 2>&1 && tail -3 $OUT/pytest_gpu.log; }; } && \
 echo "== bench" && \
-timeout -k 10 600 python -u bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err && cat $OUT/bench.json && \
+timeout -k 10 600 python -u bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err && cat $OUT/bench.json && \
 echo "== rocprofv3 kernel stats" && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run \
     -- python3 bench.py --no-cpu --roofline-only --warmup 0 "$@" > $OUT/prof_bench.json 2> $OUT/prof.err && \
