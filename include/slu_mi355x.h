@@ -309,6 +309,14 @@ typedef struct {
     int64_t npdep, zlayer, phase_last; /* 3D: layers, mine, my last phase */
 } slu_plan_stats;
 int slu_plan_get_stats(const slu_plan *p, slu_plan_stats *st);
+/* Kernel launches of the last slu_plan_factor by dispatch path (host-side
+ * counts, for tests that must prove which kernel ran).  Writes the first n of:
+ *   diag_generic, diag_f, diag_f_small, diag_wave32, diag_wave64, diag_strips,
+ *   trsm_reg64_pf, trsm_reg64_nopf, trsm_reg128_pf, trsm_reg128_nopf,
+ *   trsm_reg256_pf, trsm_reg256_nopf, trsm_blk, trsm_generic,
+ *   schur_big, schur_small, ksplit_kinfos (KInfo's of K-split updates)
+ * and returns how many there are. */
+int slu_plan_path_counts(const slu_plan *p, int64_t *out, int n);
 
 /* Last error string of this thread (empty when none). */
 const char *slu_last_error(void);

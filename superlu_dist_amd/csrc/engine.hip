@@ -581,6 +581,17 @@ struct PlanBase {
     virtual void gather_layers() { throw Error("gather_layers: not a 3D plan"); }
     virtual void adopt_factors() = 0; // upload host values that are already factors
     slu_plan_stats stats{};
+    // kernel launches of the last factor() by dispatch path (host-side counts
+    // at the launch sites, slu_plan_path_counts; the order is the ABI):
+    // the diagonal kernels, k_trsm_reg per width and PF form, k_trsm_blk,
+    // k_trsm_l / k_trsm_u, the Schur kernels, and the KInfo's of K-split updates
+    enum PathCount {
+        PC_DIAG_GENERIC, PC_DIAG_F, PC_DIAG_F_SMALL, PC_DIAG_WAVE32, PC_DIAG_WAVE64, PC_DIAG_STRIPS,
+        PC_TRSM_REG64_PF, PC_TRSM_REG64_NOPF, PC_TRSM_REG128_PF, PC_TRSM_REG128_NOPF,
+        PC_TRSM_REG256_PF, PC_TRSM_REG256_NOPF, PC_TRSM_BLK, PC_TRSM_GENERIC,
+        PC_SCHUR_BIG, PC_SCHUR_SMALL, PC_KSPLIT_KINFOS, PC_N
+    };
+    int64_t path_counts[PC_N] = {};
 };
 
 // One rank's plan for value type T (double / float / zc) over the host
@@ -2028,9 +2039,11 @@ struct Plan : PlanBase {
         double panel_flops = 0, schur_flops = 0, schur_flops_padded = 0, scatter_bytes = 0;
         double R_schur_flops = 0, R_big_flops = 0;
         i64 n_diag = 0, n_trsm_items = 0, n_schur_tiles = 0;
+        i64 n_ksplit = 0; // KInfo's of updates whose K range is split (SLU_KSPLIT_TILES)
         bool R_big = false;
     };
     vector<KInfoHost> khost;
+    i64 n_ksplit_kinfos = 0;
 
     template <typename V> static void append(V &dst, const V &src) {
         dst.insert(dst.end(), src.begin(), src.end());
@@ -2208,6 +2221,7 @@ struct Plan : PlanBase {
                 stats.n_diag += O.n_diag;
                 stats.n_trsm_items += O.n_trsm_items;
                 stats.n_schur_tiles += O.n_schur_tiles;
+                n_ksplit_kinfos += O.n_ksplit;
                 R.schur_flops += O.R_schur_flops;
                 R.big_flops += O.R_big_flops;
                 R.big = R.big || O.R_big;
@@ -2540,6 +2554,7 @@ struct Plan : PlanBase {
                 O.kinfos.push_back(kc);
                 O.khost.push_back(kh);
             }
+            if (ns > 1) O.n_ksplit += ns;
             for (int c = 0; c < ns; ++c)
                 for (int i = 0; i < tmg; ++i)
                     for (int j = 0; j < tn; ++j) {
@@ -3037,6 +3052,8 @@ struct Plan : PlanBase {
             constexpr bool P = decltype(pf)::value;
             if (ln) hipLaunchKernelGGL((k_trsm_reg<T, 0, MW, P>), dim3(ln), dim3(64 * TR_WAVES), 0, st, d_lf.p + lo);
             if (un) hipLaunchKernelGGL((k_trsm_reg<T, 1, MW, P>), dim3(un), dim3(64 * TR_WAVES), 0, su, d_uf.p + uo);
+            const int pc = MW == 64 ? PC_TRSM_REG64_PF : MW == 128 ? PC_TRSM_REG128_PF : PC_TRSM_REG256_PF;
+            path_counts[pc + (P ? 0 : 1)] += (ln != 0) + (un != 0);
         };
         auto go_pf = [&](auto maxw) {
             if (trsm_pf) go(maxw, std::true_type{});
@@ -3045,6 +3062,7 @@ struct Plan : PlanBase {
         if constexpr (cplx) {
             if (ln) hipLaunchKernelGGL((k_trsm_blk<T, 0>), dim3(ln), dim3(256), 0, st, d_lf.p + lo);
             if (un) hipLaunchKernelGGL((k_trsm_blk<T, 1>), dim3(un), dim3(256), 0, su, d_uf.p + uo);
+            path_counts[PC_TRSM_BLK] += (ln != 0) + (un != 0);
         } else if (R.tf_maxw <= 64 && trsm_narrow) {
             // narrow levels: the 64-wide instantiation (several workgroups per CU)
             go_pf(std::integral_constant<int, 64>{});
@@ -3086,6 +3104,7 @@ struct Plan : PlanBase {
     void launch_diag_wave(const LevelRange &R, double thresh, hipStream_t st) {
         if constexpr (!cplx) {
             const dim3 g((unsigned)((R.df_n + DW_WAVES - 1) / DW_WAVES)), b(64 * DW_WAVES);
+            path_counts[R.df_maxw <= 32 ? PC_DIAG_WAVE32 : PC_DIAG_WAVE64]++;
             if (R.df_maxw <= 32)
                 hipLaunchKernelGGL((k_diag_lu_w<T, 32>), g, b, 0, st, d_df.p + R.df_off, R.df_n, thresh,
                                    opts.replace_tiny_pivot, d_counters.p, d_zpiv.p);
@@ -3095,20 +3114,24 @@ struct Plan : PlanBase {
         }
     }
     void launch_strips(const LevelRange &R, double thresh, hipStream_t st) {
-        if constexpr (!cplx)
+        if constexpr (!cplx) {
             hipLaunchKernelGGL(k_diag_strips<T>, dim3(ds_grid(R.df_n)), dim3(DS_THREADS), 0, st, d_df.p + R.df_off,
                                R.df_n, d_dsflags.p + (size_t)R.df_off * DS_NFLAGS, ds_epoch, d_counters.p + 1, thresh,
                                opts.replace_tiny_pivot, d_counters.p, d_zpiv.p);
+            path_counts[PC_DIAG_STRIPS]++;
+        }
     }
     void launch_big(const LevelRange &R, int off, int cnt, hipStream_t st) {
         hipLaunchKernelGGL(k_schur_big<T>, dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
                            d_tiles_big.p + off, d_kinfo.p + R.k_off, d_L.p, d_U.p,
                            d_lblk.p, d_lmap.p, d_ublk.p, d_ucol_voff.p, d_ucol_fst.p);
+        path_counts[PC_SCHUR_BIG]++;
     }
     void launch_small(const LevelRange &R, int off, int cnt, hipStream_t st) {
         hipLaunchKernelGGL(k_schur<T>, dim3(cnt), dim3(SC_THREADS), 0, st, d_tiles.p + off,
                            d_kinfo.p + R.k_off, d_L.p, d_U.p, d_lblk.p, d_lmap.p, d_ublk.p,
                            d_ucol_voff.p, d_ucol_fst.p);
+        path_counts[PC_SCHUR_SMALL]++;
     }
 
     void issue(const vector<Sec> &secs, int off, int n_, const char *phase, int level) {
@@ -3184,6 +3207,8 @@ struct Plan : PlanBase {
         X.s = opts.serial ? stream : pstream;
         stats.n_schur_launches = 0;
         stats.n_schur_big_launches = 0;
+        std::fill(path_counts, path_counts + PC_N, 0);
+        path_counts[PC_KSPLIT_KINFOS] = n_ksplit_kinfos;
         // Look-ahead of one level on two streams:
         //   pstream: panel(L) -> [wait rest(L-1)] -> critical tiles(L) -> panel(L+1) ...
         //   stream : [wait panel(L)] -> rest tiles(L) -> [rest(L) done] ...
@@ -3208,6 +3233,7 @@ struct Plan : PlanBase {
                     hipLaunchKernelGGL(k_diag_lu<T>, dim3(R.diag_n), dim3(DIAG_THREADS), 0, P,
                                        d_diag.p + R.diag_off, thresh, opts.replace_tiny_pivot,
                                        d_counters.p, d_zpiv.p);
+                    path_counts[PC_DIAG_GENERIC]++;
                 });
             if (R.df_n)
                 span(0, P, [&] {
@@ -3215,14 +3241,17 @@ struct Plan : PlanBase {
                         launch_strips(R, thresh, P);
                     else if (R.df_maxw <= DF_SMALLW && diag_wave_ok())
                         launch_diag_wave(R, thresh, P);
-                    else if (R.df_maxw <= DF_SMALLW)
+                    else if (R.df_maxw <= DF_SMALLW) {
                         hipLaunchKernelGGL((k_diag_lu_f<T, DF_SMALLW, DF_SMALL_THREADS>), dim3(R.df_n),
                                            dim3(DF_SMALL_THREADS), 0, P, d_df.p + R.df_off, thresh,
                                            opts.replace_tiny_pivot, d_counters.p, d_zpiv.p);
-                    else
+                        path_counts[PC_DIAG_F_SMALL]++;
+                    } else {
                         hipLaunchKernelGGL(k_diag_lu_f<T>, dim3(R.df_n), dim3(DF_THREADS), 0, P,
                                            d_df.p + R.df_off, thresh, opts.replace_tiny_pivot,
                                            d_counters.p, d_zpiv.p);
+                        path_counts[PC_DIAG_F]++;
+                    }
                 });
             if (xmode && !opts.serial) {
                 // 2D grid: the exchanges on the comm stream C, the panels in
@@ -3257,6 +3286,7 @@ struct Plan : PlanBase {
                             if (R.tu_n)
                                 hipLaunchKernelGGL(k_trsm_u<T>, dim3(R.tu_n), dim3(TRSM_THREADS), 0, P,
                                                    d_tu.p + R.tu_off);
+                            path_counts[PC_TRSM_GENERIC] += (R.tl_n != 0) + (R.tu_n != 0);
                         });
                     const int pcn = R.pc_o[ch + 1] - R.pc_o[ch];
                     if (pcn)
@@ -3313,6 +3343,7 @@ struct Plan : PlanBase {
                         if (R.tu_n)
                             hipLaunchKernelGGL(k_trsm_u<T>, dim3(R.tu_n), dim3(TRSM_THREADS), 0, P,
                                                d_tu.p + R.tu_off);
+                        path_counts[PC_TRSM_GENERIC] += (R.tl_n != 0) + (R.tu_n != 0);
                     });
                 if (R.pc_n || R.ps_n)
                     span(4, P, [&] {
@@ -4693,6 +4724,7 @@ struct AmalgPlan : PlanBase {
 
     void sync_stats() {
         stats = in->stats;
+        std::copy(in->path_counts, in->path_counts + PlanBase::PC_N, this->path_counts);
         // the caller's partition's algorithmic work (what the reference's
         // pdgstrf does on this LUstruct); the coarse partition's own counts
         // (explicit zeros included) stay in the kernel-level fields
@@ -5041,6 +5073,7 @@ struct GridAmalgPlan : PlanBase {
 
     void sync_stats() {
         stats = in->stats;
+        std::copy(in->path_counts, in->path_counts + PlanBase::PC_N, this->path_counts);
         const bool cp = sizeof(T) == 16;
         const AmalgFlops &F = ch.fl; // my analysis range's share of the caller partition's work
         stats.schur_flops = F.schur * (cp ? 4.0 : 1.0);
@@ -5523,6 +5556,11 @@ void slu_plan_destroy(slu_plan *p) { delete p; }
 int slu_plan_get_stats(const slu_plan *p, slu_plan_stats *st) {
     *st = p->impl->stats;
     return 0;
+}
+
+int slu_plan_path_counts(const slu_plan *p, int64_t *out, int n) {
+    for (int i = 0; i < n && i < PlanBase::PC_N; ++i) out[i] = p->impl->path_counts[i];
+    return PlanBase::PC_N;
 }
 
 } // extern "C"

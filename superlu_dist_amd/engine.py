@@ -250,6 +250,21 @@ class Plan:
         lib().slu_plan_get_stats(self.ptr, C.byref(st))
         return st.as_dict()
 
+    PATH_KEYS = ("diag_generic", "diag_f", "diag_f_small", "diag_wave32", "diag_wave64",
+                 "diag_strips", "trsm_reg64_pf", "trsm_reg64_nopf", "trsm_reg128_pf",
+                 "trsm_reg128_nopf", "trsm_reg256_pf", "trsm_reg256_nopf", "trsm_blk",
+                 "trsm_generic", "schur_big", "schur_small", "ksplit_kinfos")
+
+    def path_counts(self):
+        """Kernel launches of the last factor() by dispatch path
+        (slu_plan_path_counts; ksplit_kinfos counts the KInfo's of K-split
+        Schur updates instead)."""
+        out = np.zeros(len(self.PATH_KEYS), dtype=np.int64)
+        n = lib().slu_plan_path_counts(self.ptr, as_i64p(out), len(out))
+        if n != len(out):
+            raise RuntimeError(f"slu_plan_path_counts: {n} counters, expected {len(out)}")
+        return dict(zip(self.PATH_KEYS, (int(v) for v in out)))
+
     def __del__(self):
         if getattr(self, "ptr", None):
             lib().slu_plan_destroy(self.ptr)

@@ -178,6 +178,7 @@ def lib():
         "slu_plan_gather3d": (C.c_int, [P]),
         "slu_plan_destroy": (None, [P]),
         "slu_plan_get_stats": (C.c_int, [P, C.POINTER(PlanStats)]),
+        "slu_plan_path_counts": (C.c_int, [P, c_i64p, C.c_int]),
         "slu_last_error": (C.c_char_p, []),
         "slu_debug_poison_lds": (C.c_int, [C.c_int]),
     }

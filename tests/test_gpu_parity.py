@@ -130,13 +130,19 @@ def test_gpu_factors_finite_with_poisoned_lds(kind, dims, dtype):
     assert err < TOL[dtype], err
 
 
-@pytest.mark.parametrize("slot_kb,dtype", [(64, 0), (1024, 1), (256, 2), (0, 0)])
-def test_gpu_overlapped_upload_download(slot_kb, dtype, monkeypatch):
+@pytest.mark.parametrize("slot_kb,dtype,d2h_mode", [
+    pytest.param(64, 0, None, id="64-0"), pytest.param(1024, 1, None, id="1024-1"),
+    pytest.param(256, 2, None, id="256-2"), pytest.param(0, 0, None, id="0-0"),
+    pytest.param(64, 0, "push", id="64-0-push"),   # SLU_D2H_MODE=push: zero-copy into the pinned slots
+])
+def test_gpu_overlapped_upload_download(slot_kb, dtype, d2h_mode, monkeypatch):
     """The drop-in path's copies (hostio.h): the values go up beside the plan
     build, each level's factors come back while later levels run, through
     pinned slots (tiny slots here, so blocks split across fills)."""
     if slot_kb:
         monkeypatch.setenv("SLU_D2H_SLOT_KB", str(slot_kb))
+    if d2h_mode:
+        monkeypatch.setenv("SLU_D2H_MODE", d2h_mode)
     kw = dict(diag=6 - 0.25, diag_im=-0.0025) if dtype == 2 else {}
     A = Csc.stencil(STENCIL_3D7, 14, 14, 14, dtype=dtype, **kw)
     S = Symbolic(A, nd_order(14, 14, 14), 60, 256)
