@@ -272,15 +272,9 @@ bool Amalg::build(int64_t n_, int ns, const int_t *xsup, const int_t *const *lid
         t0 = t;
     };
     auto W = [&](i64 k) { return (int)(xsup[k + 1] - xsup[k]); };
-    AmalgFlops fl;
+    fl = AmalgFlops{};
     std::vector<i64> ucne; // non-empty U column entries per supernode
     std::vector<int> gstart = amalg_chains(n, ns, xsup, lidx, uidx, zero_frac, maxw, 0, ns, &fl, &ucne);
-    fl_w = fl.w;
-    fl_s1 = fl.s1;
-    fl_s2 = fl.s2;
-    fl_trsm = fl.trsm;
-    fl_trsv = fl.trsv;
-    fl_schur = fl.schur;
     ns2 = (int)gstart.size();
     tick("pass 2 (chains)");
     if (ns2 == ns1) return false;

@@ -49,6 +49,11 @@ struct AmalgFlops {
     double trsm = 0;  // sum w (w + 1) m
     double trsv = 0;  // sum seglen (seglen + 1)
     double s1 = 0, s2 = 0, w = 0; // diagonal LU: w(w-1)/2, (w-1)w(2w-1)/6, w
+    // the stats' flop counts for a real / complex value type
+    double schur_flops(bool cplx) const { return schur * (cplx ? 4.0 : 1.0); }
+    double panel_flops(bool cplx) const {
+        return (cplx ? 6 * s1 + 10 * w + 8 * s2 : s1 + 2 * s2) + (cplx ? 4.0 : 1.0) * trsm + trsv;
+    }
 };
 
 // Passes 1 + 2 of the analysis over the supernodes [a0, a1): per-supernode
@@ -139,10 +144,7 @@ struct Amalg {
     // algorithmic work of the ORIGINAL partition (the reference's accounting,
     // SURVEY 8d; the plan's own counts are the coarse partition's): real-flop
     // sums, weighted by value type in the plan
-    double fl_schur = 0;          // sum over U columns of 2 * m * seglen
-    double fl_trsm = 0;           // sum w (w + 1) m
-    double fl_trsv = 0;           // sum seglen (seglen + 1)
-    double fl_s1 = 0, fl_s2 = 0, fl_w = 0; // diagonal LU: w(w-1)/2, (w-1)w(2w-1)/6, w
+    AmalgFlops fl;
 
     // Builds everything from a 1x1 LUstruct's index arrays.  Returns false
     // when no two supernodes merge (the plan then runs the original).  With

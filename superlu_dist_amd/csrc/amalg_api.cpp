@@ -84,9 +84,8 @@ int slu_amalg_apply(const void *h, int dtype, void *oL, void *oU, void *mL, void
 void slu_amalg_flops(const void *h, int dtype, double *out) {
     const Amalg *A = (const Amalg *)h;
     const bool cp = dtype == SLU_Z;
-    out[0] = A->fl_schur * (cp ? 4.0 : 1.0);
-    out[1] = (cp ? 6 * A->fl_s1 + 10 * A->fl_w + 8 * A->fl_s2 : A->fl_s1 + 2 * A->fl_s2) +
-             (cp ? 4.0 : 1.0) * A->fl_trsm + A->fl_trsv;
+    out[0] = A->fl.schur_flops(cp);
+    out[1] = A->fl.panel_flops(cp);
 }
 
 void slu_amalg_free(void *h) { delete (Amalg *)h; }
@@ -222,9 +221,8 @@ void slu_gamalg_flops(const void *h, int dtype, double *out) {
     const bool cp = dtype == SLU_Z;
     out[0] = out[1] = 0;
     for (const slu::GaChains &c : S->ch) {
-        const slu::AmalgFlops &F = c.fl;
-        out[0] += F.schur * (cp ? 4.0 : 1.0);
-        out[1] += (cp ? 6 * F.s1 + 10 * F.w + 8 * F.s2 : F.s1 + 2 * F.s2) + (cp ? 4.0 : 1.0) * F.trsm + F.trsv;
+        out[0] += c.fl.schur_flops(cp);
+        out[1] += c.fl.panel_flops(cp);
     }
 }
 

@@ -2,7 +2,7 @@
 // analysis owners, the partition, and each rank's relayout -- the structure
 // of the pieces it sends, its local coarse LUstruct and the pack / unpack
 // programs.  Host C++; the engine moves the streams and the values with its
-// transport (engine.hip, GridAmalgPlan), the CPU tests run every rank of a
+// transport (plan_amalg.h, GridAmalgPlan), the CPU tests run every rank of a
 // grid in one process (amalg_api.cpp, slu_gamalg_*).
 //
 // Stream formats (int64):

@@ -4,6 +4,7 @@
 #pragma once
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -37,6 +38,17 @@ inline std::string fmt(const char *f, ...) {
 }
 
 void set_last_error(const std::string &s);
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Integer environment switch, read at the call (never cached: the tests flip
+// these between plans of one process).
+inline int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // Host memory for large plan tables: 2 MB aligned and advised as
 // transparent huge pages, so the first touch costs one fault per 2 MB

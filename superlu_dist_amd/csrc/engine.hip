@@ -41,6 +41,8 @@
 #include <vector>
 
 #include "common.h"
+#include "devbuf.h"
+#include "xport.h"
 #include "kernels.h"
 #include "diag_strips.h"
 #include "diag_wave.h"
@@ -58,445 +60,6 @@ namespace slu {
 
 static thread_local std::string g_last_error;
 void set_last_error(const std::string &s) { g_last_error = s; }
-
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0, guard = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p - guard);
-        p = nullptr;
-        n = guard = 0;
-    }
-    void alloc(size_t cnt) {
-        release();
-        n = cnt;
-        if (cnt) HIPCHK(hipMalloc(&p, cnt * sizeof(T)));
-    }
-    // cnt elements with g more allocated on either side: a kernel may read
-    // (and mask) up to g elements outside [p, p + cnt) without a clamp
-    void alloc_guarded(size_t cnt, size_t g) {
-        release();
-        HIPCHK(hipMalloc(&p, (cnt + 2 * g) * sizeof(T)));
-        HIPCHK(hipMemset(p, 0, g * sizeof(T)));
-        HIPCHK(hipMemset(p + g + cnt, 0, g * sizeof(T)));
-        p += g;
-        n = cnt;
-        guard = g;
-    }
-    void swap(DevBuf &o) {
-        std::swap(p, o.p);
-        std::swap(n, o.n);
-        std::swap(guard, o.guard);
-    }
-    void upload(const vector<T> &v) { upload(v.data(), v.size()); }
-    void upload(const RawVec<T> &v) { upload(v.data(), v.size()); }
-    void upload(const T *h, size_t cnt) {
-        alloc(cnt);
-        if (cnt) HIPCHK(hipMemcpy(p, h, cnt * sizeof(T), hipMemcpyHostToDevice));
-    }
-    size_t bytes() const { return n * sizeof(T); }
-};
-
-} // namespace slu
-
-// ------------------------------------------------------------------ comm
-// One rank per GPU.  Production transport: RCCL communicators for the whole
-// grid, its process rows and its process columns (the reference's
-// grid->comm / rscp / cscp, SRC/superlu_grid.c:158-172).  Test transport
-// (slu_comm_create_host): host-staged broadcasts through a caller callback,
-// for several ranks sharing one GPU where RCCL refuses duplicate devices.
-struct slu_comm {
-    int nprow = 1, npcol = 1, iam = 0, myrow = 0, mycol = 0, device = 0;
-    ncclComm_t world = nullptr, row = nullptr, col = nullptr;
-    // 3D grids (SRC/superlu_grid3d.c: Pz layers of a Pr x Pc grid, the
-    // reference's grid3d->zscp): world / row / col above are the layer's,
-    // zcomm joins the ranks at my (row, column) position of every layer
-    int npdep = 1, zlayer = 0;
-    ncclComm_t all = nullptr, zcomm = nullptr;
-    slu_host_bcast_fn host_fn = nullptr;
-    slu_host_p2p_fn host_p2p = nullptr; // point-to-point test transport
-    void *host_ctx = nullptr;
-    // exchange watchdog (watchdog.h), created with the first exchange
-    std::unique_ptr<slu::Watchdog> wd;
-    bool wd_init = false;
-    slu::Watchdog *watchdog() {
-        if (wd_init) return wd.get();
-        wd_init = true;
-        const double b = slu::Watchdog::bound_from_env();
-        if (b <= 0) return nullptr;
-        wd.reset(new slu::Watchdog);
-        wd->bound_s = b;
-        wd->device = device;
-        char w[160];
-        snprintf(w, sizeof w, "rank %d of a %dx%d%s grid (row %d, column %d%s), %s transport", iam, nprow, npcol,
-                 npdep > 1 ? ("x" + std::to_string(npdep)).c_str() : "", myrow, mycol,
-                 npdep > 1 ? (", layer " + std::to_string(zlayer)).c_str() : "",
-                 world || zcomm ? "RCCL" : host_p2p ? "host point-to-point" : "host broadcast");
-        wd->who = w;
-        if (world || zcomm) {
-            ncclComm_t cs[5] = {row, col, world, zcomm, all};
-            wd->abort_comms = [cs] {
-                for (ncclComm_t cm : cs)
-                    if (cm) ncclCommAbort(cm);
-            };
-            wd->async_error = [cs]() -> std::string {
-                static const char *names[5] = {"row", "column", "layer", "z", "world"};
-                for (int i = 0; i < 5; ++i) {
-                    ncclResult_t r = ncclSuccess;
-                    if (!cs[i] || ncclCommGetAsyncError(cs[i], &r) != ncclSuccess) continue;
-                    if (r != ncclSuccess && r != ncclInProgress)
-                        return std::string(names[i]) + " communicator: " + ncclGetErrorString(r);
-                }
-                return "";
-            };
-        }
-        return wd.get();
-    }
-};
-
-namespace slu {
-
-using i64 = int64_t;
-
-enum { G_WORLD = 0, G_ROW = 1, G_COL = 2, G_Z = 3 };
-
-// Grouped broadcasts of device buffers within the world / a process row /
-// a process column.  Ops are queued and issued together by flush() (one
-// ncclGroupStart/End); every member of a communicator queues the same ops in
-// the same order, which the plan guarantees by construction.
-struct Xport {
-    slu_comm *c = nullptr;
-    hipStream_t s = nullptr;
-    struct Op {
-        int g, root;
-        void *buf; // null on a member that does not need the section
-        size_t bytes;
-        uint32_t mask; // members (group ranks) that receive it
-    };
-    vector<Op> ops;
-    vector<char> hbuf;
-    double sent = 0, recvd = 0; // bytes this rank moved (RCCL sections)
-    // what the next flush() is, for the watchdog's diagnostics
-    const char *phase = "plan-time exchange";
-    int level = -1;
-    int gsize(int g) const {
-        return g == G_WORLD ? c->nprow * c->npcol : g == G_ROW ? c->npcol : g == G_COL ? c->nprow : c->npdep;
-    }
-    int grank(int g) const {
-        return g == G_WORLD ? c->iam : g == G_ROW ? c->mycol : g == G_COL ? c->myrow : c->zlayer;
-    }
-    ncclComm_t comm_of(int g) const {
-        return g == G_WORLD ? c->world : g == G_ROW ? c->row : g == G_COL ? c->col : c->zcomm;
-    }
-    void bcast(int g, int root, void *buf, size_t bytes) {
-        if (bytes && gsize(g) > 1) ops.push_back({g, root, buf, bytes, ~0u});
-    }
-    // A section of root's data for the members in mask (the reference sends
-    // L(:,k) only to the process columns flagged in ToSendR,
-    // SRC/pdgstrf.c:1039-1044, SRC/pddistribute.c:779).  Every member of the
-    // group queues the op (buf = null when not in mask), so that the host
-    // transport, which can only broadcast, stays in step.
-    void section(int g, int root, uint32_t mask, void *buf, size_t bytes) {
-        if (bytes && gsize(g) > 1 && (mask & ~(1u << root))) ops.push_back({g, root, buf, bytes, mask});
-    }
-    // This rank's point-to-point calls for the queued group, in issue order:
-    // a section (and a broadcast, mask = all) becomes the root's sends to
-    // every other member in the mask, in member order, and each member's
-    // receive from the root.  The RCCL branch issues exactly this list as
-    // ncclSend / ncclRecv inside one ncclGroupStart / End, and the
-    // point-to-point test transport hands exactly this list to its callback
-    // (staged through host memory, all posted before any completes), so the
-    // send / receive pairing every grid test runs is the one the RCCL node
-    // runs (tests/test_grid.py::test_rccl_call_sequence_is_the_tested_one_cpu
-    // compares the two lists and checks the pairing across ranks).
-    struct P2P {
-        int g, peer, send; // group, group rank of the other side, 1 = send
-        size_t bytes;
-        int op; // index into ops
-    };
-    vector<P2P> expand() const {
-        vector<P2P> q;
-        for (size_t i = 0; i < ops.size(); ++i) {
-            const Op &o = ops[i];
-            const int me = grank(o.g), P = gsize(o.g);
-            if (me == o.root) {
-                for (int m = 0; m < P; ++m)
-                    if (m != me && (o.mask >> m & 1)) q.push_back({o.g, m, 1, o.bytes, (int)i});
-            } else if (o.mask >> me & 1) {
-                q.push_back({o.g, o.root, 0, o.bytes, (int)i});
-            }
-        }
-        return q;
-    }
-    int world_of(int g, int m) const {
-        return g == G_WORLD ? m : g == G_ROW ? c->myrow * c->npcol + m : g == G_COL ? m * c->npcol + c->mycol : c->iam;
-    }
-    // SLU_XPORT_TRACE=<dir>: every flush appends this rank's call list to
-    // <dir>/xport_<kind>.<world rank> (kind: the list the transport ran, and
-    // on the host transports also "rccl", the calls the RCCL branch would
-    // issue for the same group, recorded by a dry run of flush_rccl)
-    const char *trace_dir = getenv("SLU_XPORT_TRACE");
-    long trace_seq = 0;
-    void trace(const char *kind, const vector<P2P> &q) const {
-        if (!trace_dir) return;
-        char fn[1024];
-        snprintf(fn, sizeof fn, "%s/xport_%s.%d", trace_dir, kind, c->iam);
-        FILE *f = fopen(fn, "a");
-        if (!f) return;
-        fprintf(f, "F %ld %s %d\n", trace_seq, phase, level);
-        for (const P2P &p : q)
-            fprintf(f, "%c %d %d %zu\n", p.send ? 'S' : 'R', p.g, world_of(p.g, p.peer), p.bytes);
-        fclose(f);
-    }
-    vector<vector<char>> p2p_bufs;
-    bool host_mem = false; // schedule-only plans: buffers are host memory
-    void flush_p2p() {
-        const vector<P2P> q0 = expand();
-        trace("host", q0);
-        if (trace_dir) flush_rccl(true);
-        vector<slu_host_p2p_op> q;
-        if (host_mem) {
-            // no staging: the host buffers go to the transport as they are
-            for (const P2P &p : q0) {
-                const Op &o = ops[p.op];
-                SLU_REQUIRE(o.buf, "section of group %d root %d has no buffer", o.g, o.root);
-                q.push_back({p.g, p.peer, p.send, 0, o.buf, (int64_t)p.bytes});
-                (p.send ? sent : recvd) += (double)p.bytes;
-            }
-            if (!q.empty())
-                SLU_REQUIRE(c->host_p2p(c->host_ctx, (int)q.size(), q.data()) == 0,
-                            "host point-to-point group of %zu ops failed", q.size());
-            return;
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        // one host staging buffer per op: the root's D2H once, its sends read it
-        p2p_bufs.resize(std::max(p2p_bufs.size(), ops.size()));
-        vector<char> staged(ops.size(), 0);
-        for (const P2P &p : q0) {
-            const Op &o = ops[p.op];
-            SLU_REQUIRE(o.buf, "section of group %d root %d has no buffer", o.g, o.root);
-            vector<char> &hb = p2p_bufs[p.op];
-            hb.resize(o.bytes);
-            if (p.send && !staged[p.op]) {
-                HIPCHK(hipMemcpyAsync(hb.data(), o.buf, o.bytes, hipMemcpyDeviceToHost, s));
-                staged[p.op] = 1;
-            }
-            q.push_back({p.g, p.peer, p.send, 0, hb.data(), (int64_t)p.bytes});
-            (p.send ? sent : recvd) += (double)p.bytes;
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        if (!q.empty())
-            SLU_REQUIRE(c->host_p2p(c->host_ctx, (int)q.size(), q.data()) == 0,
-                        "host point-to-point group of %zu ops failed", q.size());
-        for (const P2P &p : q0)
-            if (!p.send)
-                HIPCHK(hipMemcpyAsync(ops[p.op].buf, p2p_bufs[p.op].data(), p.bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    // this rank's part of the queued group, for the watchdog
-    std::string describe() const {
-        static const char *gn[4] = {"layer", "row", "column", "z"};
-        std::string s = phase;
-        if (level >= 0) s += " of level " + std::to_string(level);
-        int shown = 0, more = 0;
-        double sb = 0, rb = 0;
-        std::string lst;
-        auto add = [&](bool send, int g, int m, size_t bytes) {
-            (send ? sb : rb) += (double)bytes;
-            if (shown == 12) {
-                ++more;
-                return;
-            }
-            char b[160];
-            if (g == G_Z)
-                snprintf(b, sizeof b, "%s layer %d: %zu bytes", send ? "send to" : "receive from", m, bytes);
-            else
-                snprintf(b, sizeof b, "%s %s peer %d (rank %d): %zu bytes", send ? "send to" : "receive from",
-                         gn[g], m, world_of(g, m), bytes);
-            lst += (shown++ ? "; " : "") + std::string(b);
-        };
-        for (const P2P &p : expand()) add(p.send != 0, p.g, p.peer, p.bytes);
-        char b[160];
-        snprintf(b, sizeof b, " (%zu ops; this rank sends %.0f and receives %.0f bytes): ", ops.size(), sb, rb);
-        s += b + lst;
-        if (more) s += "; ... " + std::to_string(more) + " more";
-        return s;
-    }
-    void flush() {
-        if (ops.empty()) return;
-        ++trace_seq;
-        Watchdog *wd = c->watchdog();
-        if (c->host_p2p || c->host_fn) {
-            // host transports block in the callback: the record is open for its duration
-            const uint64_t id = wd ? wd->open(describe(), nullptr) : 0;
-            if (c->host_p2p) flush_host_p2p();
-            else {
-                if (trace_dir) flush_rccl(true);
-                flush_host_bcast();
-            }
-            if (wd) wd->close(id);
-            ops.clear();
-            return;
-        }
-        flush_rccl(false);
-        if (wd) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            HIPCHK(hipEventRecord(e, s));
-            wd->open(describe(), e);
-        }
-        ops.clear();
-    }
-    void flush_host_p2p() { flush_p2p(); }
-    void flush_host_bcast() {
-        {
-            HIPCHK(hipStreamSynchronize(s));
-            for (auto &o : ops) {
-                hbuf.resize(o.bytes);
-                const int me = grank(o.g);
-                const bool root = me == o.root;
-                // copies on the transport's stream and waited for: a pageable
-                // hipMemcpy returns once the host buffer is staged, before the
-                // DMA has landed, and kernels on a non-blocking stream could
-                // read the destination first
-                if (root) {
-                    HIPCHK(hipMemcpyAsync(hbuf.data(), o.buf, o.bytes, hipMemcpyDeviceToHost, s));
-                    HIPCHK(hipStreamSynchronize(s));
-                }
-                SLU_REQUIRE(c->host_fn(c->host_ctx, o.g, o.root, hbuf.data(), (int64_t)o.bytes) == 0,
-                            "host broadcast (group %d, root %d, %zu bytes) failed", o.g, o.root,
-                            o.bytes);
-                if (!root && (o.mask >> me & 1)) {
-                    SLU_REQUIRE(o.buf, "section of group %d root %d has no buffer", o.g, o.root);
-                    HIPCHK(hipMemcpyAsync(o.buf, hbuf.data(), o.bytes, hipMemcpyHostToDevice, s));
-                    HIPCHK(hipStreamSynchronize(s));
-                }
-            }
-        }
-    }
-    // Every op as direct sends from the root to each member that needs it
-    // (xGMI is point to point: a root's sends to its row / column peers use
-    // distinct links; the plan-time all-gathers' broadcasts too, so there is
-    // one call sequence, expand()'s, for RCCL and the tested transport).
-    // dry: record the calls (SLU_XPORT_TRACE, kind "rccl") instead of
-    // issuing them -- the host transports' check of this very code path.
-    void flush_rccl(bool dry) {
-        const vector<P2P> q = expand();
-        if (dry) {
-            trace("rccl", q);
-            return;
-        }
-        trace("rccl", q);
-        NCCLCHK(ncclGroupStart());
-        for (const P2P &p : q) {
-            const Op &o = ops[p.op];
-            if (p.send) NCCLCHK(ncclSend(o.buf, o.bytes, ncclChar, p.peer, comm_of(o.g), s));
-            else NCCLCHK(ncclRecv(o.buf, o.bytes, ncclChar, p.peer, comm_of(o.g), s));
-            (p.send ? sent : recvd) += (double)p.bytes;
-        }
-        NCCLCHK(ncclGroupEnd());
-    }
-    // plan-time all-to-all of variable-length int64 blobs in the world
-    // group: out[q] goes to rank q, the result's [p] came from rank p.  Sizes
-    // first (an all-gather), then one section per ordered pair, queued in
-    // the same order on every rank.
-    vector<vector<i64>> alltoallv(const vector<vector<i64>> &out) {
-        const int P = gsize(G_WORLD), me = grank(G_WORLD);
-        SLU_REQUIRE((int)out.size() == P && P <= 32, "alltoallv over %d ranks", P);
-        vector<vector<i64>> in(P);
-        in[me] = out[me];
-        if (P == 1) return in;
-        vector<i64> mine(P);
-        for (int q = 0; q < P; ++q) mine[q] = (i64)out[q].size();
-        const vector<vector<i64>> sz = allgatherv(G_WORLD, mine); // sz[p][q]
-        for (int p = 0; p < P; ++p)
-            if (p != me) in[p].resize(sz[p][me]);
-        if (host_mem) {
-            for (int p = 0; p < P; ++p)
-                for (int q = 0; q < P; ++q) {
-                    if (p == q || !sz[p][q]) continue;
-                    void *buf = me == p ? (void *)out[q].data() : me == q ? (void *)in[p].data() : nullptr;
-                    section(G_WORLD, p, 1u << q, buf, (size_t)sz[p][q] * sizeof(i64));
-                }
-            flush();
-            return in;
-        }
-        vector<i64> so(P + 1, 0), ro(P + 1, 0);
-        for (int q = 0; q < P; ++q) {
-            so[q + 1] = so[q] + (q == me ? 0 : sz[me][q]);
-            ro[q + 1] = ro[q] + (q == me ? 0 : sz[q][me]);
-        }
-        DevBuf<i64> ds, dr;
-        ds.alloc(std::max<i64>(so[P], 1));
-        dr.alloc(std::max<i64>(ro[P], 1));
-        for (int q = 0; q < P; ++q)
-            if (q != me && sz[me][q])
-                HIPCHK(hipMemcpy(ds.p + so[q], out[q].data(), sz[me][q] * sizeof(i64), hipMemcpyHostToDevice));
-        for (int p = 0; p < P; ++p)
-            for (int q = 0; q < P; ++q) {
-                if (p == q || !sz[p][q]) continue;
-                void *buf = me == p ? (void *)(ds.p + so[q]) : me == q ? (void *)(dr.p + ro[p]) : nullptr;
-                section(G_WORLD, p, 1u << q, buf, (size_t)sz[p][q] * sizeof(i64));
-            }
-        flush();
-        HIPCHK(hipStreamSynchronize(s));
-        for (int p = 0; p < P; ++p)
-            if (p != me && sz[p][me])
-                HIPCHK(hipMemcpy(in[p].data(), dr.p + ro[p], sz[p][me] * sizeof(i64), hipMemcpyDeviceToHost));
-        return in;
-    }
-    // plan-time all-gather of variable-length int64 blobs within group g
-    vector<vector<i64>> allgatherv(int g, const vector<i64> &mine) {
-        const int P = gsize(g), me = grank(g);
-        vector<vector<i64>> out(P);
-        if (P == 1) {
-            out[0] = mine;
-            return out;
-        }
-        if (host_mem) { // the same broadcasts over host buffers
-            vector<i64> sz(P, 0);
-            sz[me] = (i64)mine.size();
-            for (int r = 0; r < P; ++r) bcast(g, r, &sz[r], sizeof(i64));
-            flush();
-            for (int r = 0; r < P; ++r) {
-                out[r] = r == me ? mine : vector<i64>(sz[r]);
-                bcast(g, r, out[r].data(), sz[r] * sizeof(i64));
-            }
-            flush();
-            return out;
-        }
-        DevBuf<i64> dsz;
-        dsz.alloc(P);
-        vector<i64> sz(P, 0);
-        sz[me] = (i64)mine.size();
-        HIPCHK(hipMemcpy(dsz.p, sz.data(), P * sizeof(i64), hipMemcpyHostToDevice));
-        for (int r = 0; r < P; ++r) bcast(g, r, dsz.p + r, sizeof(i64));
-        flush();
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipMemcpy(sz.data(), dsz.p, P * sizeof(i64), hipMemcpyDeviceToHost));
-        vector<i64> off(P + 1, 0);
-        for (int r = 0; r < P; ++r) off[r + 1] = off[r] + sz[r];
-        DevBuf<i64> d;
-        d.alloc(std::max<i64>(off[P], 1));
-        if (!mine.empty())
-            HIPCHK(hipMemcpy(d.p + off[me], mine.data(), mine.size() * sizeof(i64),
-                             hipMemcpyHostToDevice));
-        for (int r = 0; r < P; ++r) bcast(g, r, d.p + off[r], sz[r] * sizeof(i64));
-        flush();
-        HIPCHK(hipStreamSynchronize(s));
-        for (int r = 0; r < P; ++r) {
-            out[r].resize(sz[r]);
-            if (sz[r])
-                HIPCHK(hipMemcpy(out[r].data(), d.p + off[r], sz[r] * sizeof(i64),
-                                 hipMemcpyDeviceToHost));
-        }
-        return out;
-    }
-};
 
 struct LevelRange {
     int diag_off = 0, diag_n = 0;
@@ -563,6 +126,160 @@ __global__ void __launch_bounds__(256) k_zranges(const ZRange *r, T *L, T *U, T 
         else v[i] = b[i];
     }
 }
+
+// Event timing of one factor() (opts.timing: 0 records nothing, 1 the totals
+// in the stats, 2 also a per-level table on stderr).  A span is a pair of
+// events around a step on its stream.
+struct FactorTimer {
+    int timing = 0;
+    vector<hipEvent_t> ev;
+    // kind: 0 diag, 1 trsm, 2 schur (128x128 tiles), 3 schur (64x64), 4 comm
+    struct Span { int a, b, kind, level; };
+    vector<Span> spans;
+    int cur_level = 0, e_start = -1, e_end = -1, e_ph = -1, zstart = -1;
+    vector<int> lvl_end;
+    vector<std::array<int, 3>> zmarks; // (phase start, phase end, reduction end) events
+    FactorTimer() = default;
+    FactorTimer(const FactorTimer &) = delete;
+    FactorTimer &operator=(const FactorTimer &) = delete;
+    ~FactorTimer() { reset(0); }
+    void reset(int timing_) {
+        for (auto e : ev) (void)hipEventDestroy(e);
+        ev.clear();
+        spans.clear();
+        lvl_end.clear();
+        zmarks.clear();
+        timing = timing_;
+    }
+    int mark(hipStream_t st) {
+        if (!timing) return -1;
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipEventRecord(e, st));
+        ev.push_back(e);
+        return (int)ev.size() - 1;
+    }
+    template <typename F> void span(int kind, hipStream_t st, F &&fn) {
+        const int a = mark(st);
+        fn();
+        if (timing) spans.push_back({a, mark(st), kind, cur_level});
+    }
+    void start(hipStream_t st) { e_start = zstart = mark(st); }
+    void end(hipStream_t st) { e_end = mark(st); }
+    void level(int L) { cur_level = L; }
+    void level_end(hipStream_t st) {
+        if (timing >= 2) lvl_end.push_back(mark(st));
+    }
+    // 3D grids: my phase's levels are done / its ancestor reduction is done
+    void phase_end(hipStream_t st) { e_ph = mark(st); }
+    void reduce_end(hipStream_t st) {
+        if (!timing) return;
+        const int e_red = mark(st);
+        zmarks.push_back({zstart, e_ph, e_red});
+        zstart = e_red;
+    }
+    float ms(int a, int b) const {
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, ev[a], ev[b]));
+        return t;
+    }
+    // after the streams are synchronised: the totals into stats, the table
+    void finish(slu_plan_stats &stats, const vector<LevelRange> &levels, const vector<vector<int>> &bylev, int iam) {
+        if (!timing) return;
+        stats.t_total_ms = ms(e_start, e_end);
+        stats.t_diag_ms = stats.t_trsm_ms = stats.t_schur_ms = stats.t_schur_big_ms = 0;
+        stats.t_comm_ms = 0;
+        stats.schur_big_flops = 0;
+        vector<std::array<double, 5>> t(levels.size(), {0, 0, 0, 0, 0}); // per level and kind
+        for (auto &s : spans) {
+            const float d = ms(s.a, s.b);
+            t[s.level][s.kind] += d;
+            if (s.kind == 0) stats.t_diag_ms += d;
+            else if (s.kind == 1) stats.t_trsm_ms += d;
+            else if (s.kind == 4) stats.t_comm_ms += d;
+            else {
+                stats.t_schur_ms += d;
+                if (s.kind == 2) stats.t_schur_big_ms += d;
+            }
+        }
+        for (auto &R : levels) stats.schur_big_flops += R.big_flops;
+        for (int i = 0; i < 8; ++i) stats.t_phase_ms[i] = 0;
+        stats.t_zreduce_ms = 0;
+        for (size_t i = 0; i < zmarks.size() && i < 8; ++i) {
+            stats.t_phase_ms[i] = ms(zmarks[i][0], zmarks[i][1]);
+            stats.t_zreduce_ms += ms(zmarks[i][1], zmarks[i][2]);
+        }
+        if (timing >= 2) { // per-level breakdown (stderr)
+            fprintf(stderr, "[slu rank %d] lvl nsup diag trsm big small atomic  GFLOP  diag_ms trsm_ms big_ms small_ms comm_ms  TF/s wall_ms\n", iam);
+            for (size_t L = 0; L < levels.size(); ++L) {
+                const LevelRange &R = levels[L];
+                double sch = t[L][2] + t[L][3];
+                const float wall = ms(L ? lvl_end[L - 1] : e_start, lvl_end[L]);
+                fprintf(stderr, "[slu rank %d] %3zu %5zu %4d %5d %5d %5d %6d %7.2f %8.3f %7.3f %7.3f %7.3f %7.3f %6.2f %7.3f\n",
+                        iam, L, bylev[L].size(), R.diag_n + R.df_n, R.lf_n + R.uf_n + R.tl_n + R.tu_n,
+                        R.big_n, R.tile_n, R.atomic_tiles, R.schur_flops / 1e9, t[L][0], t[L][1], t[L][2], t[L][3],
+                        t[L][4], sch > 0 ? R.schur_flops / sch / 1e9 : 0.0, (double)wall);
+            }
+        }
+        reset(0);
+    }
+};
+
+// Slot of the overlapped D2H's pinned-slot pipeline (Plan::run_d2h);
+// SLU_D2H_SLOT_KB overrides it: tests use tiny slots so that blocks split
+// across fills.
+inline i64 d2h_slot_bytes() {
+    const char *e = getenv("SLU_D2H_SLOT_KB");
+    return e ? std::max<i64>(16, atoll(e)) << 10 : 128ll << 20;
+}
+
+struct D2HFill {
+    int level;          // all blocks final after ev_pan[level]
+    int seg_off, seg_n; // PushSeg range
+    int hs_off, hs_n;   // HostSeg range
+    i64 bytes;
+};
+struct HostSeg {
+    char *host;
+    i64 off, bytes; // in the slot
+};
+// The fills of the overlapped D2H: the plan enumerates its (device range,
+// host pointer) pairs level by level, this packs them into slots.
+struct D2HFills {
+    i64 slot = d2h_slot_bytes(), min_fill = slot / 4;
+    static constexpr i64 PIECE = 1ll << 20;
+    vector<D2HFill> fills;
+    vector<PushSeg> h_push;
+    vector<HostSeg> h_unpack;
+    DevBuf<PushSeg> d_push;
+    i64 fb = 0; // bytes in the open fill
+    int seg0 = 0, hs0 = 0;
+    void close(int L) {
+        if (fb == 0) return;
+        fills.push_back({L, seg0, (int)h_push.size() - seg0, hs0, (int)h_unpack.size() - hs0, fb});
+        seg0 = (int)h_push.size();
+        hs0 = (int)h_unpack.size();
+        fb = 0;
+    }
+    void add(const char *dev, char *host, i64 bytes, int L) {
+        i64 done = 0;
+        while (done < bytes) {
+            const i64 take = std::min(bytes - done, slot - fb);
+            for (i64 o = 0; o < take; o += PIECE)
+                h_push.push_back({dev + done + o, fb + o, (int)std::min(PIECE, take - o)});
+            // host pieces of <= 4 MB so the unpack threads balance
+            for (i64 o = 0; o < take; o += 4 * PIECE)
+                h_unpack.push_back({host + done + o, fb + o, std::min(4 * PIECE, take - o)});
+            fb += (take + 15) & ~(i64)15; // 16-byte aligned slot offsets
+            done += take;
+            if (fb >= slot) close(L);
+        }
+    }
+    void end_level(int L, bool last) {
+        if (fb >= min_fill || last) close(L);
+    }
+    void finish() { d_push.upload(h_push.empty() ? vector<PushSeg>(1) : h_push); }
+};
 
 struct PlanBase {
     virtual ~PlanBase() = default;
@@ -702,7 +419,7 @@ struct Plan : PlanBase {
     // SLU_3D_SOLO=1 (measurement hook, tools/model3d.py): one layer alone on
     // a GPU -- the reductions pack / add but exchange nothing, so each
     // layer's phase times can be taken without the others running beside it
-    bool zsolo = getenv("SLU_3D_SOLO") && atoi(getenv("SLU_3D_SOLO")) == 1;
+    bool zsolo = env_int("SLU_3D_SOLO", 0) == 1;
     vector<DiagItem<T>> diag_items;
     vector<TrsmLItem<T>> tl_items;
     vector<TrsmUItem<T>> tu_items;
@@ -764,8 +481,7 @@ struct Plan : PlanBase {
         if (o) opts = *o;
         xmode = Pr * Pc > 1;
         if (xmode) {
-            const char *e = getenv("SLU_PANEL_CHUNKS");
-            pchunks = std::max(1, std::min(NCHM, e ? atoi(e) : 4));
+            pchunks = std::max(1, std::min(NCHM, env_int("SLU_PANEL_CHUNKS", 4)));
         }
         SLU_REQUIRE(!xmode || (comm && (comm->world || comm->host_fn || comm->host_p2p)),
                     "a %dx%d grid needs a communicator (slu_comm_create)", Pr, Pc);
@@ -813,34 +529,22 @@ struct Plan : PlanBase {
         // (created on a helper thread beside the host-side plan build --
         // the first streams of a process take ~35 ms -- and joined before
         // their first use)
-        std::string stream_err;
-        std::thread stream_thread([this, &stream_err] {
-            try {
-                if (comm) HIPCHK(hipSetDevice(comm->device));
-                int prio_lo = 0, prio_hi = 0;
-                const auto ts0 = std::chrono::steady_clock::now();
-                HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-                HIPCHK(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio_lo));
-                HIPCHK(hipStreamCreateWithPriority(&pstream, hipStreamNonBlocking, prio_hi));
-                HIPCHK(hipStreamCreateWithPriority(&ustream, hipStreamNonBlocking, prio_hi));
-                if (xmode) HIPCHK(hipStreamCreateWithPriority(&cstream, hipStreamNonBlocking, prio_hi));
-                if (getenv("SLU_PROFILE_PLAN"))
-                    fprintf(stderr, "[slu plan %d] streams               %6.1f ms (helper thread)\n", iam,
-                            ms_since(ts0));
-            } catch (const std::exception &e) {
-                stream_err = e.what();
-            }
+        HelperThread stream_thread;
+        stream_thread.start(device(), [this] {
+            int prio_lo = 0, prio_hi = 0;
+            const auto ts0 = std::chrono::steady_clock::now();
+            HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+            HIPCHK(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio_lo));
+            HIPCHK(hipStreamCreateWithPriority(&pstream, hipStreamNonBlocking, prio_hi));
+            HIPCHK(hipStreamCreateWithPriority(&ustream, hipStreamNonBlocking, prio_hi));
+            if (xmode) HIPCHK(hipStreamCreateWithPriority(&cstream, hipStreamNonBlocking, prio_hi));
+            if (getenv("SLU_PROFILE_PLAN"))
+                fprintf(stderr, "[slu plan %d] streams               %6.1f ms (helper thread)\n", iam,
+                        ms_since(ts0));
         });
-        struct Joiner { // (an exception before the join must not leave it joinable)
-            std::thread &t;
-            ~Joiner() {
-                if (t.joinable()) t.join();
-            }
-        } stream_joiner{stream_thread};
         auto join_streams = [&] {
-            if (!stream_thread.joinable()) return;
+            if (!stream_thread.running()) return;
             stream_thread.join();
-            SLU_REQUIRE(stream_err.empty(), "%s", stream_err.c_str());
             X.s = pstream;
         };
         int_t *hx = LU->Glu_persist->xsup;
@@ -870,62 +574,41 @@ struct Plan : PlanBase {
         if (opts.overlap_upload) {
             // the H2D copy of the values runs beside the rest of the plan
             // build (index exchange, levels, schedule, device tables)
-            up_thread = std::thread([this] {
-                try {
-                    HIPCHK(hipSetDevice(comm ? comm->device : 0));
-                    upload_values();
-                } catch (const std::exception &e) {
-                    up_err = e.what();
-                }
-            });
+            up_thread.start(device(), [this] { upload_values(); });
         }
         if (opts.overlap_download) {
             // the pinned D2H slots (hipHostMalloc, ~0.1 s the first time in a
             // process) are allocated beside the plan build too
-            if (const char *e = getenv("SLU_D2H_SLOT_KB")) {
-                D2H_SLOT = std::max<i64>(16, atoll(e)) << 10;
-                D2H_MIN = D2H_SLOT / 4;
-            }
-            pin_thread = std::thread([this] {
-                try {
-                    HIPCHK(hipSetDevice(comm ? comm->device : 0));
-                    // get() frees slots of another size: never while a
-                    // run_d2h (which holds `use`) still copies through them
-                    std::lock_guard<std::mutex> in_use(pinned_pool(1).use);
-                    pinned_pool(1).get(D2H_NS, D2H_SLOT);
-                } catch (const std::exception &e) {
-                    pin_err = e.what();
-                }
+            pin_thread.start(device(), [this] {
+                // get() frees slots of another size: never while a
+                // run_d2h (which holds `use`) still copies through them
+                std::lock_guard<std::mutex> in_use(pinned_pool(1).use);
+                pinned_pool(1).get(D2H_NS, d2h.slot);
             });
         }
-        try {
-            build_local();
-            tick("build_local");
-            exchange_index();
-            exchange_needs();
-            tick("exchange_index");
-            compute_levels();
-            tick("compute_levels");
-            layout_values();
-            tick("layout_values");
-            if (zmode) build_zranges(true);
-            build_schedule();
-            if (prof)
-                fprintf(stderr, "[slu plan %d]   (add_supernode %.1f ms, merge + atomics %.1f ms: "
-                                "resize %.1f, copy %.1f, tiles %.1f)\n",
-                        iam, t_addsn, t_merge, t_resize, t_put, t_tiles);
-            tick("build_schedule");
-            join_streams();
-            build_device();
-            tick("build_device");
-            build_d2h();
-            tick("build_d2h");
-        } catch (...) {
-            if (stream_thread.joinable()) stream_thread.join();
-            if (up_thread.joinable()) up_thread.join();
-            if (pin_thread.joinable()) pin_thread.join();
-            throw;
-        }
+        // (an exception from here on: the helper threads are joined by their
+        // destructors, stream_thread's first)
+        build_local();
+        tick("build_local");
+        exchange_index();
+        exchange_needs();
+        tick("exchange_index");
+        compute_levels();
+        tick("compute_levels");
+        layout_values();
+        tick("layout_values");
+        if (zmode) build_zranges(true);
+        build_schedule();
+        if (prof)
+            fprintf(stderr, "[slu plan %d]   (add_supernode %.1f ms, merge + atomics %.1f ms: "
+                            "resize %.1f, copy %.1f, tiles %.1f)\n",
+                    iam, t_addsn, t_merge, t_resize, t_put, t_tiles);
+        tick("build_schedule");
+        join_streams();
+        build_device();
+        tick("build_device");
+        build_d2h();
+        tick("build_d2h");
         stats.t_plan_ms = ms_since(t0);
     }
 
@@ -987,17 +670,8 @@ struct Plan : PlanBase {
                         memset(arena + (size_t)sc.off * sizeof(T), 0, bytes);
                     }
                 }
-                for (int i = a0; i < a1; ++i) {
-                    const Sec &sc = secs[i];
-                    X.section(sc.g, sc.root, sc.mask,
-                              sc.off >= 0 ? arena + (size_t)sc.off * sizeof(T) : nullptr,
-                              (size_t)sc.cnt * sizeof(T));
-                }
-                X.phase = ph ? "L/U panel exchange (replay)" : "diagonal-package exchange (replay)";
-                X.level = (int)L;
-                X.flush();
-                X.phase = "plan-time exchange";
-                X.level = -1;
+                issue(secs, a0, a1 - a0, ph ? "L/U panel exchange (replay)" : "diagonal-package exchange (replay)",
+                      (int)L, (T *)hd.data(), (T *)hp.data());
                 for (int i = a0; i < a1; ++i) {
                     const Sec &sc = secs[i];
                     const int me = sc.g == G_ROW ? mycol : myrow;
@@ -1023,11 +697,7 @@ struct Plan : PlanBase {
             if (!recv)
                 for (size_t b = 0; b < bytes; ++b) zb[b] = pat(1000000 + zp, 0, root, iam, b);
             X.section(G_Z, root, 1u << (recv ? zl : peer), zb.data(), bytes);
-            X.phase = "3D ancestor reduction (replay)";
-            X.level = zp;
-            X.flush();
-            X.phase = "plan-time exchange";
-            X.level = -1;
+            X.flush_as("3D ancestor reduction (replay)", zp);
             if (recv && bytes) {
                 for (size_t b = 0; b < bytes; ++b)
                     SLU_REQUIRE(zb[b] == pat(1000000 + zp, 0, root, iam, b),
@@ -1060,14 +730,13 @@ struct Plan : PlanBase {
         tprev = now;
     }
 
-    static double ms_since(std::chrono::steady_clock::time_point t0) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-            .count();
-    }
+    int device() const { return comm ? comm->device : 0; }
 
     ~Plan() override {
-        if (up_thread.joinable()) up_thread.join();
-        if (pin_thread.joinable()) pin_thread.join();
+        // (before the streams and events go; the DevBuf members are covered
+        // by the declaration order, see up_thread)
+        up_thread.wait();
+        pin_thread.wait();
         for (auto e : ev_pan) (void)hipEventDestroy(e);
         for (auto e : ev_rest) (void)hipEventDestroy(e);
         if (ev_start) (void)hipEventDestroy(ev_start);
@@ -1671,11 +1340,7 @@ struct Plan : PlanBase {
         X.s = st;
         if (!zsolo) {
             X.section(G_Z, recv ? peer : zl, 1u << (recv ? zl : peer), d_zbuf.p, (size_t)cnt * sizeof(T));
-            X.phase = "3D ancestor reduction";
-            X.level = p;
-            X.flush();
-            X.phase = "plan-time exchange";
-            X.level = -1;
+            X.flush_as("3D ancestor reduction", p);
         }
         zbytes += (double)cnt * sizeof(T);
         if (recv) launch_zranges(a, b, ZR_ADD, st);
@@ -1715,11 +1380,7 @@ struct Plan : PlanBase {
                                    (int)ZR_PACK);
             X.s = st;
             X.section(G_Z, sender, 1u << (recv ? zl : peer), buf.p, (size_t)bo * sizeof(T));
-            X.phase = "3D gather to layer 0";
-            X.level = il;
-            X.flush();
-            X.phase = "plan-time exchange";
-            X.level = -1;
+            X.flush_as("3D gather to layer 0", il);
             if (recv && nr)
                 hipLaunchKernelGGL(k_zranges<T>, dim3(nr), dim3(256), 0, st, dr.p, d_L.p, d_U.p, buf.p,
                                    (int)ZR_COPY);
@@ -2713,8 +2374,6 @@ struct Plan : PlanBase {
     int snap_state = 0;
 
     // ---- host <-> HBM copies of the values (hostio.h)
-    std::thread up_thread, pin_thread;
-    std::string up_err, pin_err; // one per helper thread (no shared writes)
     double up_ms = 0;
     bool host_current = false; // the host LUstruct holds what the device holds
 
@@ -2741,7 +2400,7 @@ struct Plan : PlanBase {
     void upload_values() {
         const auto t0 = std::chrono::steady_clock::now();
         vector<Xfer> xs = value_xfers();
-        staged_h2d(xs, comm ? comm->device : 0);
+        staged_h2d(xs, device());
         double b = 0;
         for (auto &x : xs) b += (double)x.bytes;
         stats.h2d_bytes = b;
@@ -2750,25 +2409,13 @@ struct Plan : PlanBase {
 
     void upload() override {
         const auto t0 = std::chrono::steady_clock::now();
-        if (pin_thread.joinable()) pin_thread.join();
-        if (!pin_err.empty()) {
-            if (up_thread.joinable()) up_thread.join();
-            std::string e;
-            e.swap(pin_err);
-            throw Error(e);
-        }
-        if (up_thread.joinable()) {
-            up_thread.join();
-            if (!up_err.empty()) {
-                std::string e;
-                e.swap(up_err);
-                throw Error(e);
-            }
-            stats.t_upload_wait_ms = ms_since(t0);
-        } else {
-            upload_values();
-            stats.t_upload_wait_ms = ms_since(t0);
-        }
+        const bool overlapped = up_thread.running();
+        pin_thread.wait();
+        up_thread.wait(); // (both have stopped before either's error is thrown)
+        pin_thread.join();
+        up_thread.join();
+        if (!overlapped) upload_values();
+        stats.t_upload_wait_ms = ms_since(t0);
         stats.t_upload_ms = up_ms;
         vstate = 1;
         d_acur = nullptr;
@@ -2785,72 +2432,32 @@ struct Plan : PlanBase {
     // finished blocks are pushed by a small kernel (k_push) into a pinned
     // slot of <= SLOT bytes ("fill"), and host threads scatter the slot into
     // the caller's arrays while the next fill is pushed.
-    // slot / minimum fill (SLU_D2H_SLOT_KB overrides the slot: tests use tiny
-    // slots so that blocks split across fills)
-    i64 D2H_SLOT = 128ll << 20, D2H_MIN = 32ll << 20;
-    static constexpr i64 D2H_PIECE = 1ll << 20;
     static constexpr int D2H_NS = 4; // pinned slots in flight
-    struct D2HFill {
-        int level;        // all blocks final after ev_pan[level]
-        int seg_off, seg_n; // PushSeg range
-        int hs_off, hs_n; // HostSeg range
-        i64 bytes;
-    };
-    struct HostSeg {
-        char *host;
-        i64 off, bytes; // in the slot
-    };
-    vector<D2HFill> d2h_fills;
+    D2HFills d2h;
     // called on the D2H stream before fill F's push, after its level's
     // panels are done (AmalgPlan: compress the level into the caller's layout)
     std::function<void(int, hipStream_t)> d2h_pre;
-    vector<PushSeg> h_push;
-    vector<HostSeg> h_unpack;
-    DevBuf<PushSeg> d_push;
     DevBuf<char> d_stage; // HBM staging slots of the D2H (SDMA mode)
 
     void build_d2h() {
         if (!opts.overlap_download) return;
         LocalLU *Llu = LU->Llu;
-        i64 fb = 0; // bytes in the open fill
-        int seg0 = 0, hs0 = 0;
-        auto close = [&](int L) {
-            if (fb == 0) return;
-            d2h_fills.push_back({L, seg0, (int)h_push.size() - seg0, hs0, (int)h_unpack.size() - hs0, fb});
-            seg0 = (int)h_push.size();
-            hs0 = (int)h_unpack.size();
-            fb = 0;
-        };
-        auto add = [&](const char *dev, char *host, i64 bytes, int L) {
-            i64 done = 0;
-            while (done < bytes) {
-                const i64 take = std::min(bytes - done, D2H_SLOT - fb);
-                for (i64 o = 0; o < take; o += D2H_PIECE)
-                    h_push.push_back({dev + done + o, fb + o, (int)std::min(D2H_PIECE, take - o)});
-                // host pieces of <= 4 MB so the unpack threads balance
-                for (i64 o = 0; o < take; o += 4 * D2H_PIECE)
-                    h_unpack.push_back({host + done + o, fb + o, std::min(4 * D2H_PIECE, take - o)});
-                fb += (take + 15) & ~(i64)15; // 16-byte aligned slot offsets
-                done += take;
-                if (fb >= D2H_SLOT) close(L);
-            }
-        };
         for (size_t L = 0; L < levels.size(); ++L) {
             for (int k : bylev[L]) {
                 if (k % Pc == mycol && lval_off[k / Pc] >= 0) {
                     const int ljb = k / Pc;
-                    add((const char *)(d_L.p + lval_off[ljb]), (char *)Llu->Lnzval_bc_ptr[ljb],
-                        (i64)lval_ld[ljb] * W(k) * (i64)sizeof(T), (int)L);
+                    d2h.add((const char *)(d_L.p + lval_off[ljb]), (char *)Llu->Lnzval_bc_ptr[ljb],
+                            (i64)lval_ld[ljb] * W(k) * (i64)sizeof(T), (int)L);
                 }
                 if (k % Pr == myrow && uval_off[k / Pr] >= 0) {
                     const int lb = k / Pr;
-                    add((const char *)(d_U.p + uval_off[lb]), (char *)Llu->Unzval_br_ptr[lb],
-                        (i64)Llu->Ufstnz_br_ptr[lb][1] * (i64)sizeof(T), (int)L);
+                    d2h.add((const char *)(d_U.p + uval_off[lb]), (char *)Llu->Unzval_br_ptr[lb],
+                            (i64)Llu->Ufstnz_br_ptr[lb][1] * (i64)sizeof(T), (int)L);
                 }
             }
-            if (fb >= D2H_MIN || L + 1 == levels.size()) close((int)L);
+            d2h.end_level((int)L, L + 1 == levels.size());
         }
-        d_push.upload(h_push.empty() ? vector<PushSeg>(1) : h_push);
+        d2h.finish();
     }
 
     // The D2H pipeline (runs on a helper thread during factor()): this
@@ -2859,10 +2466,10 @@ struct Plan : PlanBase {
     // its push event has fired (parallel host memcpy).
     void run_d2h(double &bytes, int64_t &ncopies) {
         double t_wait_push = 0, t_unpack = 0, t_wait_slot = 0;
-        HIPCHK(hipSetDevice(comm ? comm->device : 0));
+        HIPCHK(hipSetDevice(device()));
         constexpr int NS = D2H_NS;
         std::lock_guard<std::mutex> in_use(pinned_pool(1).use);
-        std::vector<char *> slot = pinned_pool(1).get(NS, D2H_SLOT);
+        std::vector<char *> slot = pinned_pool(1).get(NS, d2h.slot);
         hipStream_t cs = nullptr;
         hipEvent_t evf[NS] = {};
         std::mutex mu;
@@ -2876,7 +2483,7 @@ struct Plan : PlanBase {
             fail = true;
             cv.notify_all();
         };
-        const int nf = (int)d2h_fills.size();
+        const int nf = (int)d2h.fills.size();
         std::thread unpacker;
         try {
             int prio_lo = 0, prio_hi = 0;
@@ -2888,11 +2495,11 @@ struct Plan : PlanBase {
             const int nwg = ge ? std::max(1, atoi(ge)) : 128; // (32: +25 ms of tail at 100^3, tools/d2h_variants.py)
             const char *me = getenv("SLU_D2H_MODE"); // diagnostics: push (zero-copy) | sdma
             const bool use_sdma = !(me && !strcmp(me, "push"));
-            if (use_sdma && d_stage.n < (size_t)NS * D2H_SLOT) d_stage.alloc((size_t)NS * D2H_SLOT);
+            if (use_sdma && d_stage.n < (size_t)NS * d2h.slot) d_stage.alloc((size_t)NS * d2h.slot);
             for (auto &e : evf) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
             unpacker = std::thread([&] {
                 try {
-                    HIPCHK(hipSetDevice(comm ? comm->device : 0));
+                    HIPCHK(hipSetDevice(device()));
                     for (int j = 0; j < nf; ++j) {
                         {
                             std::unique_lock<std::mutex> lk(mu);
@@ -2903,14 +2510,14 @@ struct Plan : PlanBase {
                         HIPCHK(hipEventSynchronize(evf[j % NS]));
                         const auto tu = std::chrono::steady_clock::now();
                         t_wait_push += std::chrono::duration<double, std::milli>(tu - tw).count();
-                        const D2HFill &F = d2h_fills[j];
+                        const D2HFill &F = d2h.fills[j];
                         const char *src = slot[j % NS];
                         parallel_for(F.hs_n, [&](int i) {
-                            const HostSeg &h = h_unpack[F.hs_off + i];
+                            const HostSeg &h = d2h.h_unpack[F.hs_off + i];
                             memcpy(h.host, src + h.off, (size_t)h.bytes);
                         }, 1);
                         t_unpack += ms_since(tu);
-                        for (int i = 0; i < F.hs_n; ++i) bytes += (double)h_unpack[F.hs_off + i].bytes;
+                        for (int i = 0; i < F.hs_n; ++i) bytes += (double)d2h.h_unpack[F.hs_off + i].bytes;
                         ncopies += F.hs_n;
                         std::lock_guard<std::mutex> lk(mu);
                         unpacked = j + 1;
@@ -2928,21 +2535,21 @@ struct Plan : PlanBase {
                     t_wait_slot += ms_since(tw);
                     if (fail) break;
                 }
-                const D2HFill &F = d2h_fills[j];
+                const D2HFill &F = d2h.fills[j];
                 HIPCHK(hipStreamWaitEvent(cs, ev_pan[F.level], 0));
                 if (d2h_pre) d2h_pre(F.level, cs); // (amalgamated plan: relayout of the levels)
                 if (use_sdma) {
                     // gather into an HBM slot (HBM-bound, microseconds), then
                     // one DMA-engine copy to the pinned slot: the PCIe-bound
                     // part occupies no CU while the factorization runs
-                    char *ds = d_stage.p + (size_t)(j % NS) * D2H_SLOT;
+                    char *ds = d_stage.p + (size_t)(j % NS) * d2h.slot;
                     hipLaunchKernelGGL(k_push, dim3(std::min(F.seg_n, 4 * nwg)), dim3(256), 0, cs,
-                                       (const PushSeg *)(d_push.p + F.seg_off), F.seg_n, ds);
+                                       (const PushSeg *)(d2h.d_push.p + F.seg_off), F.seg_n, ds);
                     HIPCHK(hipGetLastError());
                     HIPCHK(hipMemcpyAsync(slot[j % NS], ds, (size_t)F.bytes, hipMemcpyDeviceToHost, cs));
                 } else {
                     hipLaunchKernelGGL(k_push, dim3(std::min(F.seg_n, nwg)), dim3(256), 0, cs,
-                                       (const PushSeg *)(d_push.p + F.seg_off), F.seg_n, slot[j % NS]);
+                                       (const PushSeg *)(d2h.d_push.p + F.seg_off), F.seg_n, slot[j % NS]);
                     HIPCHK(hipGetLastError());
                 }
                 HIPCHK(hipEventRecord(evf[j % NS], cs));
@@ -3024,18 +2631,18 @@ struct Plan : PlanBase {
     // this split their K range (default 0, off: the chunks of a destination
     // add atomically in no fixed order, so the root levels' factors would not
     // be bit-reproducible from run to run, for ~0.3 ms at 100^3)
-    int ksplit_tiles = getenv("SLU_KSPLIT_TILES") ? atoi(getenv("SLU_KSPLIT_TILES")) : 0;
+    int ksplit_tiles = env_int("SLU_KSPLIT_TILES", 0);
     // SLU_TRSM_NARROW: 0 the 256-wide k_trsm_reg everywhere, 1 the 64-wide
     // instantiation for levels whose TRSM supernodes are <= 64 wide, 2 (default)
     // also the 128-wide one for <= 128
-    int trsm_narrow = getenv("SLU_TRSM_NARROW") ? atoi(getenv("SLU_TRSM_NARROW")) : 2;
+    int trsm_narrow = env_int("SLU_TRSM_NARROW", 2);
     // SLU_TRSM_2STREAM=1 (default): the U panel's TRSM on a stream of its
     // own beside the L panel's (both only wait for the diagonal block; near
     // the root each is a few slabs, latency-bound)
-    int trsm_2stream = getenv("SLU_TRSM_2STREAM") ? atoi(getenv("SLU_TRSM_2STREAM")) : 1;
+    int trsm_2stream = env_int("SLU_TRSM_2STREAM", 1);
     // SLU_TRSM_PF=1 (default): k_trsm_reg's latency form (next block's T and
     // Dinv loaded during the current block, columns stored when final)
-    int trsm_pf = getenv("SLU_TRSM_PF") ? atoi(getenv("SLU_TRSM_PF")) : 1;
+    int trsm_pf = env_int("SLU_TRSM_PF", 1);
     // the level's fast-path TRSM items, or (ch >= 0) those of exchange chunk ch
     void launch_trsm_fast(const LevelRange &R, hipStream_t st, int ch = -1) {
         const int lo = R.lf_off + (ch >= 0 ? R.lf_o[ch] : 0), ln = ch >= 0 ? R.lf_o[ch + 1] - R.lf_o[ch] : R.lf_n;
@@ -3085,21 +2692,21 @@ struct Plan : PlanBase {
     // would wait for the whole level.  Where the first launch drains they get
     // CUs and run beside the second (100^3: 363 -> 345 ms; more split points
     // gain nothing further, tools/ab_env.sh).
-    int rest_split = getenv("SLU_REST_SPLIT") ? atoi(getenv("SLU_REST_SPLIT")) : 30;
+    int rest_split = env_int("SLU_REST_SPLIT", 30);
     // k_diag_strips (diag_strips.h) for the levels near the root: a few wide
     // real blocks, each factored by one workgroup per 32-column strip
     // (SLU_DIAG_STRIPS=0: k_diag_lu_f everywhere; SLU_DIAG_STRIPS_MAX: the
     // most blocks a level may hold for it, default 32)
     // (SLU_DIAG_STRIPS=2, test hook: every fast level, narrow blocks too)
-    int strips_mode = getenv("SLU_DIAG_STRIPS") ? atoi(getenv("SLU_DIAG_STRIPS")) : 1;
-    int strips_max = getenv("SLU_DIAG_STRIPS_MAX") ? atoi(getenv("SLU_DIAG_STRIPS_MAX")) : 32;
+    int strips_mode = env_int("SLU_DIAG_STRIPS", 1);
+    int strips_max = env_int("SLU_DIAG_STRIPS_MAX", 32);
     bool strips_ok(const LevelRange &R) const {
         if (cplx || strips_mode == 0) return false;
         return strips_mode == 2 || (R.df_maxw > DF_SMALLW && R.df_n <= strips_max);
     }
     // k_diag_lu_w (diag_wave.h): one wave per narrow diagonal block, real
     // types (SLU_DIAG_WAVE=0: k_diag_lu_f's 256-thread path instead)
-    int diag_wave = getenv("SLU_DIAG_WAVE") ? atoi(getenv("SLU_DIAG_WAVE")) : 1;
+    int diag_wave = env_int("SLU_DIAG_WAVE", 1);
     bool diag_wave_ok() const { return !cplx && diag_wave != 0; }
     void launch_diag_wave(const LevelRange &R, double thresh, hipStream_t st) {
         if constexpr (!cplx) {
@@ -3134,321 +2741,173 @@ struct Plan : PlanBase {
         path_counts[PC_SCHUR_SMALL]++;
     }
 
-    void issue(const vector<Sec> &secs, int off, int n_, const char *phase, int level) {
+    // One exchange group of a level: the sections [off, off + n_) out of the
+    // diagonal-package arena dpk / the panel arena pan (factor(): d_dpk /
+    // d_pan; check_exchange(): its host arenas)
+    void issue(const vector<Sec> &secs, int off, int n_, const char *phase, int level, T *dpk, T *pan) {
         for (int i = off; i < off + n_; ++i) {
             const Sec &s = secs[i];
-            T *base = s.arena ? d_pan.p : d_dpk.p;
+            T *base = s.arena ? pan : dpk;
             X.section(s.g, s.root, s.mask, s.off >= 0 ? base + s.off : nullptr,
                       (size_t)s.cnt * sizeof(T));
         }
-        X.phase = phase;
-        X.level = level;
-        X.flush();
-        X.phase = "plan-time exchange";
-        X.level = -1;
+        X.flush_as(phase, level);
     }
 
     // ------------------------------------------------------- factor
-    void factor(double anorm, int *info, int *tiny) override {
-        SLU_REQUIRE(vstate == 1, "factor: no unfactored values on the device (%s)",
-                    vstate == 2 ? "already factored; upload / restore / fill_a first"
-                                : "upload or fill_a first");
-        vstate = 2;
-        a_fact = d_acur;
-        // thresh = smach_dist("Epsilon") * anorm (SRC/pdgstrf.c:412-413); in
-        // psgstrf thresh is a float product.
-        const float s_eps = 5.9604644775390625e-08f; // FLT_EPSILON * 0.5
-        double thresh = sizeof(T) == 4 ? (double)(float)(s_eps * (float)anorm) : (double)s_eps * anorm;
-        HIPCHK(hipMemsetAsync(d_counters.p, 0, d_counters.bytes(), stream));
-        if (++ds_epoch >= 0x7fffffffu) { // (strip flags: a new epoch per factorization)
-            HIPCHK(hipMemsetAsync(d_dsflags.p, 0, d_dsflags.bytes(), stream));
-            ds_epoch = 1;
-        }
-        HIPCHK(hipMemsetAsync(d_zpiv.p, 0, d_zpiv.bytes(), stream));
-#ifdef SLU_SB_STAMP
-        {
-            const unsigned z = 0;
-            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(slu_stamp_n), &z, sizeof z));
-        }
-#endif
-        const bool timing = opts.timing != 0;
-        vector<hipEvent_t> ev;
-        auto mark = [&]() -> int {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            HIPCHK(hipEventRecord(e, stream));
-            ev.push_back(e);
-            return (int)ev.size() - 1;
-        };
-        // kind: 0 diag, 1 trsm, 2 schur (128x128 tiles), 3 schur (64x64), 4 comm
-        struct Span { int a, b, kind, level; };
-        vector<Span> spans;
-        int cur_level = 0;
-        auto mark_on = [&](hipStream_t st) -> int {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            HIPCHK(hipEventRecord(e, st));
-            ev.push_back(e);
-            return (int)ev.size() - 1;
-        };
-        auto span = [&](int kind, hipStream_t st, auto &&fn) {
-            int a = timing ? mark_on(st) : -1;
-            fn();
-            if (timing) spans.push_back({a, mark_on(st), kind, cur_level});
-        };
-        if (zmode) { // ancestor forests another layer factors start from zero
-            launch_zranges(zr_off[0], zr_off[1], ZR_ZERO, stream);
-            zbytes = 0;
-        }
-        int e_start = timing ? mark() : -1;
-        vector<int> lvl_end;
-        HIPCHK(hipEventRecord(ev_start, stream));
-        HIPCHK(hipStreamWaitEvent(pstream, ev_start, 0));
-        X.s = opts.serial ? stream : pstream;
-        stats.n_schur_launches = 0;
-        stats.n_schur_big_launches = 0;
-        std::fill(path_counts, path_counts + PC_N, 0);
-        path_counts[PC_KSPLIT_KINFOS] = n_ksplit_kinfos;
-        // Look-ahead of one level on two streams:
-        //   pstream: panel(L) -> [wait rest(L-1)] -> critical tiles(L) -> panel(L+1) ...
-        //   stream : [wait panel(L)] -> rest tiles(L) -> [rest(L) done] ...
-        // Critical tiles update exactly the destinations in the panels of
-        // level L+1, so panel(L+1) (diag LU, TRSM, exchanges) runs beside the
-        // bulk of level L's Schur update (SRC/pdgstrf.c:1115-1356 look-ahead).
-        // 3D grids: my phases one after the other, each followed by its
-        // ancestor reduction (SRC/pdgstrf3d.c:300-345)
-        const int nph = zmode ? my_last + 1 : 1;
-        int last_L = -1;
-        vector<std::array<int, 3>> zmarks; // (phase start, phase end, reduction end) events
-        int zstart = e_start;
-        for (int ph = 0; ph < nph; ++ph) {
-        const size_t L0 = zmode ? phase_lv[ph] : 0, L1 = zmode ? phase_lv[ph + 1] : levels.size();
-        for (size_t L = L0; L < L1; ++L) {
-            const LevelRange &R = levels[L];
-            cur_level = (int)L;
-            last_L = (int)L;
-            hipStream_t P = opts.serial ? stream : pstream;
-            if (R.diag_n)
-                span(0, P, [&] {
-                    hipLaunchKernelGGL(k_diag_lu<T>, dim3(R.diag_n), dim3(DIAG_THREADS), 0, P,
-                                       d_diag.p + R.diag_off, thresh, opts.replace_tiny_pivot,
-                                       d_counters.p, d_zpiv.p);
-                    path_counts[PC_DIAG_GENERIC]++;
-                });
-            if (R.df_n)
-                span(0, P, [&] {
-                    if (strips_ok(R))
-                        launch_strips(R, thresh, P);
-                    else if (R.df_maxw <= DF_SMALLW && diag_wave_ok())
-                        launch_diag_wave(R, thresh, P);
-                    else if (R.df_maxw <= DF_SMALLW) {
-                        hipLaunchKernelGGL((k_diag_lu_f<T, DF_SMALLW, DF_SMALL_THREADS>), dim3(R.df_n),
-                                           dim3(DF_SMALL_THREADS), 0, P, d_df.p + R.df_off, thresh,
-                                           opts.replace_tiny_pivot, d_counters.p, d_zpiv.p);
-                        path_counts[PC_DIAG_F_SMALL]++;
-                    } else {
-                        hipLaunchKernelGGL(k_diag_lu_f<T>, dim3(R.df_n), dim3(DF_THREADS), 0, P,
-                                           d_df.p + R.df_off, thresh, opts.replace_tiny_pivot,
-                                           d_counters.p, d_zpiv.p);
-                        path_counts[PC_DIAG_F]++;
-                    }
-                });
-            if (xmode && !opts.serial) {
-                // 2D grid: the exchanges on the comm stream C, the panels in
-                // R.nch chunks.  P: TRSM(c) -> pack(c) -> [C: send / receive
-                // chunk c] for every c, so chunk c + 1's TRSM runs beside
-                // chunk c's transfer; the critical tiles of chunk c (P) and
-                // its rest tiles (Schur stream) start when chunk c is in.
-                hipStream_t C = cstream;
-                auto exchange = [&](const vector<Sec> &secs, int off, int cnt, const char *what, hipEvent_t done) {
-                    HIPCHK(hipEventRecord(ev_pk, P));
-                    HIPCHK(hipStreamWaitEvent(C, ev_pk, 0));
-                    X.s = C;
-                    if (cnt) span(4, C, [&] { issue(secs, off, cnt, what, (int)L); });
-                    HIPCHK(hipEventRecord(done, C));
-                };
-                if (R.dc_n || R.ds_n) {
-                    if (R.dc_n)
-                        span(4, P, [&] {
-                            hipLaunchKernelGGL(k_copy<T>, dim3(R.dc_n), dim3(256), 0, P, d_dcopy.p + R.dc_off);
-                        });
-                    exchange(dsecs, R.ds_off, R.ds_n, "diagonal-package exchange", ev_dx);
-                    HIPCHK(hipStreamWaitEvent(P, ev_dx, 0));
-                }
-                for (int ch = 0; ch < R.nch; ++ch) {
-                    if (R.lf_o[ch + 1] > R.lf_o[ch] || R.uf_o[ch + 1] > R.uf_o[ch])
-                        span(1, P, [&] { launch_trsm_fast(R, P, ch); });
-                    if (ch == 0 && (R.tl_n || R.tu_n)) // (wide supernodes' generic items: all in chunk 0)
-                        span(1, P, [&] {
-                            if (R.tl_n)
-                                hipLaunchKernelGGL(k_trsm_l<T>, dim3(R.tl_n), dim3(TRSM_THREADS), 0, P,
-                                                   d_tl.p + R.tl_off);
-                            if (R.tu_n)
-                                hipLaunchKernelGGL(k_trsm_u<T>, dim3(R.tu_n), dim3(TRSM_THREADS), 0, P,
-                                                   d_tu.p + R.tu_off);
-                            path_counts[PC_TRSM_GENERIC] += (R.tl_n != 0) + (R.tu_n != 0);
-                        });
-                    const int pcn = R.pc_o[ch + 1] - R.pc_o[ch];
-                    if (pcn)
-                        span(4, P, [&] {
-                            hipLaunchKernelGGL(k_copy<T>, dim3(pcn), dim3(256), 0, P, d_pcopy.p + R.pc_off + R.pc_o[ch]);
-                        });
-                    exchange(psecs, R.ps_off + R.ps_o[ch], R.ps_o[ch + 1] - R.ps_o[ch], "L/U panel exchange",
-                             ev_cx[ch]);
-                }
-                // critical tiles of L on the panel stream, after the rest of L-1
-                if (L > 0) HIPCHK(hipStreamWaitEvent(P, ev_rest[L - 1], 0));
-                for (int ch = 0; ch < R.nch; ++ch) {
-                    HIPCHK(hipStreamWaitEvent(P, ev_cx[ch], 0));
-                    const int nb = R.bc_o[ch + 1] - R.bc_o[ch], nsm = R.sc_o[ch + 1] - R.sc_o[ch];
-                    if (nb) {
-                        span(2, P, [&] { launch_big(R, R.big_off + R.bc_o[ch], nb, P); });
-                        stats.n_schur_launches++;
-                        stats.n_schur_big_launches++;
-                    }
-                    if (nsm) {
-                        span(3, P, [&] { launch_small(R, R.tile_off + R.sc_o[ch], nsm, P); });
-                        stats.n_schur_launches++;
-                    }
-                }
-                HIPCHK(hipEventRecord(ev_pan[L], P));
-                // the rest of L on the Schur stream, chunk by chunk as they arrive
-                for (int ch = 0; ch < R.nch; ++ch) {
-                    HIPCHK(hipStreamWaitEvent(stream, ev_cx[ch], 0));
-                    const int nb = R.br_o[ch + 1] - R.br_o[ch], nsm = R.sr_o[ch + 1] - R.sr_o[ch];
-                    if (nb) {
-                        span(2, stream, [&] { launch_big(R, R.big_off + R.bigc_n + R.br_o[ch], nb, stream); });
-                        stats.n_schur_launches++;
-                        stats.n_schur_big_launches++;
-                    }
-                    if (nsm) {
-                        span(3, stream, [&] { launch_small(R, R.tile_off + R.tilec_n + R.sr_o[ch], nsm, stream); });
-                        stats.n_schur_launches++;
-                    }
-                }
-            } else {
-                if (R.dc_n || R.ds_n)
-                    span(4, P, [&] {
-                        if (R.dc_n)
-                            hipLaunchKernelGGL(k_copy<T>, dim3(R.dc_n), dim3(256), 0, P,
-                                               d_dcopy.p + R.dc_off);
-                        issue(dsecs, R.ds_off, R.ds_n, "diagonal-package exchange", (int)L);
-                    });
-                if (R.lf_n || R.uf_n) span(1, P, [&] { launch_trsm_fast(R, P); });
-                if (R.tl_n || R.tu_n)
-                    span(1, P, [&] {
-                        if (R.tl_n)
-                            hipLaunchKernelGGL(k_trsm_l<T>, dim3(R.tl_n), dim3(TRSM_THREADS), 0, P,
-                                               d_tl.p + R.tl_off);
-                        if (R.tu_n)
-                            hipLaunchKernelGGL(k_trsm_u<T>, dim3(R.tu_n), dim3(TRSM_THREADS), 0, P,
-                                               d_tu.p + R.tu_off);
-                        path_counts[PC_TRSM_GENERIC] += (R.tl_n != 0) + (R.tu_n != 0);
-                    });
-                if (R.pc_n || R.ps_n)
-                    span(4, P, [&] {
-                        if (R.pc_n)
-                            hipLaunchKernelGGL(k_copy<T>, dim3(R.pc_n), dim3(256), 0, P,
-                                               d_pcopy.p + R.pc_off);
-                        issue(psecs, R.ps_off, R.ps_n, "L/U panel exchange", (int)L);
-                    });
-                HIPCHK(hipEventRecord(ev_pan[L], P));
-                // critical tiles of L on the panel stream, after the rest of L-1
-                if (L > 0) HIPCHK(hipStreamWaitEvent(P, ev_rest[L - 1], 0));
-                if (R.bigc_n) {
-                    span(2, P, [&] { launch_big(R, R.big_off, R.bigc_n, P); });
-                    stats.n_schur_launches++;
-                    stats.n_schur_big_launches++;
-                }
-                if (R.tilec_n) {
-                    span(3, P, [&] { launch_small(R, R.tile_off, R.tilec_n, P); });
-                    stats.n_schur_launches++;
-                }
-                // the rest of L on the Schur stream, once the panels of L exist
-                HIPCHK(hipStreamWaitEvent(stream, ev_pan[L], 0));
-                if (R.big_n > R.bigc_n) {
-                    // the first rest_split %% of the rest tiles as a launch of their own
-                    const int nrest = R.big_n - R.bigc_n;
-                    const int n1 = rest_split > 0 && !opts.serial ? (int)((i64)nrest * rest_split / 100) : 0;
-                    span(2, stream, [&] {
-                        if (n1 > 0) launch_big(R, R.big_off + R.bigc_n, n1, stream);
-                        if (nrest > n1) launch_big(R, R.big_off + R.bigc_n + n1, nrest - n1, stream);
-                    });
-                    stats.n_schur_launches++;
-                    stats.n_schur_big_launches++;
-                }
-                if (R.tile_n > R.tilec_n) {
-                    span(3, stream, [&] {
-                        launch_small(R, R.tile_off + R.tilec_n, R.tile_n - R.tilec_n, stream);
-                    });
-                    stats.n_schur_launches++;
-                }
-            }
-            HIPCHK(hipEventRecord(ev_rest[L], stream));
-            if (opts.timing >= 2) lvl_end.push_back(mark_on(stream)); // level wall time
-        }
-        if (zmode) {
-            hipStream_t P = opts.serial ? stream : pstream;
-            if (last_L >= 0) HIPCHK(hipStreamWaitEvent(P, ev_rest[last_L], 0));
-            const int e_ph = timing ? mark_on(P) : -1;
-            if (ph < maxlvl - 1) {
-                span(4, P, [&] { zreduce(ph, P); });
-                HIPCHK(hipEventRecord(ev_pend, P));
-                HIPCHK(hipStreamWaitEvent(stream, ev_pend, 0));
-            }
-            if (timing) {
-                const int e_red = mark_on(P);
-                zmarks.push_back({zstart, e_ph, e_red});
-                zstart = e_red;
-            }
-        }
-        }
-        if (xmode && !opts.serial) { // the comm stream's last group before the end of the factorization
-            HIPCHK(hipEventRecord(ev_pend, cstream));
-            HIPCHK(hipStreamWaitEvent(stream, ev_pend, 0));
-        }
-        X.s = opts.serial ? stream : pstream;
-        HIPCHK(hipEventRecord(ev_pend, pstream));
-        HIPCHK(hipStreamWaitEvent(stream, ev_pend, 0));
-        HIPCHK(hipGetLastError());
-        int e_end = timing ? mark() : -1;
-        std::thread d2h;
-        std::string d2h_err;
-        double d2h_ms = 0;
-        int64_t ncopies = 0;
-        double dbytes = 0;
-        const bool overlap_dl = opts.overlap_download != 0;
-        // diagnostics: SLU_D2H_AFTER=1 starts the D2H only after the device
-        // finished the factorization (no overlap, same copy path)
-        const bool d2h_after = overlap_dl && getenv("SLU_D2H_AFTER");
-        if (d2h_after) sync();
-        if (overlap_dl) {
-            d2h = std::thread([&] {
-                const auto t0 = std::chrono::steady_clock::now();
-                try {
-                    run_d2h(dbytes, ncopies);
-                } catch (const std::exception &e) {
-                    d2h_err = e.what();
-                }
-                d2h_ms = ms_since(t0);
+    // Leaf steps of a level, shared by the two level bodies below.  tm is
+    // the event timing of the factorization under way.
+    FactorTimer tm;
+
+    // the level's diagonal blocks
+    void diag_step(const LevelRange &R, double thresh, hipStream_t P) {
+        if (R.diag_n)
+            tm.span(0, P, [&] {
+                hipLaunchKernelGGL(k_diag_lu<T>, dim3(R.diag_n), dim3(DIAG_THREADS), 0, P,
+                                   d_diag.p + R.diag_off, thresh, opts.replace_tiny_pivot,
+                                   d_counters.p, d_zpiv.p);
+                path_counts[PC_DIAG_GENERIC]++;
             });
+        if (R.df_n)
+            tm.span(0, P, [&] {
+                if (strips_ok(R))
+                    launch_strips(R, thresh, P);
+                else if (R.df_maxw <= DF_SMALLW && diag_wave_ok())
+                    launch_diag_wave(R, thresh, P);
+                else if (R.df_maxw <= DF_SMALLW) {
+                    hipLaunchKernelGGL((k_diag_lu_f<T, DF_SMALLW, DF_SMALL_THREADS>), dim3(R.df_n),
+                                       dim3(DF_SMALL_THREADS), 0, P, d_df.p + R.df_off, thresh,
+                                       opts.replace_tiny_pivot, d_counters.p, d_zpiv.p);
+                    path_counts[PC_DIAG_F_SMALL]++;
+                } else {
+                    hipLaunchKernelGGL(k_diag_lu_f<T>, dim3(R.df_n), dim3(DF_THREADS), 0, P,
+                                       d_df.p + R.df_off, thresh, opts.replace_tiny_pivot,
+                                       d_counters.p, d_zpiv.p);
+                    path_counts[PC_DIAG_F]++;
+                }
+            });
+    }
+    // the generic TRSM items (supernodes wider than the fast path's)
+    void trsm_generic(const LevelRange &R, hipStream_t P) {
+        if (!R.tl_n && !R.tu_n) return;
+        tm.span(1, P, [&] {
+            if (R.tl_n)
+                hipLaunchKernelGGL(k_trsm_l<T>, dim3(R.tl_n), dim3(TRSM_THREADS), 0, P, d_tl.p + R.tl_off);
+            if (R.tu_n)
+                hipLaunchKernelGGL(k_trsm_u<T>, dim3(R.tu_n), dim3(TRSM_THREADS), 0, P, d_tu.p + R.tu_off);
+            path_counts[PC_TRSM_GENERIC] += (R.tl_n != 0) + (R.tu_n != 0);
+        });
+    }
+    // pack copies (2D grids): the diagonal packages / cnt panel-section items from off
+    void pack_diag(const LevelRange &R, hipStream_t P) {
+        if (R.dc_n) hipLaunchKernelGGL(k_copy<T>, dim3(R.dc_n), dim3(256), 0, P, d_dcopy.p + R.dc_off);
+    }
+    void pack_panels(int off, int cnt, hipStream_t P) {
+        if (cnt) hipLaunchKernelGGL(k_copy<T>, dim3(cnt), dim3(256), 0, P, d_pcopy.p + off);
+    }
+    // One Schur launch of n 128x128 tiles from off (its first n1, if any, as
+    // a kernel launch of their own: one launch in the stats, two in
+    // path_counts) / of n 64x64 tiles
+    void schur_big(const LevelRange &R, int off, int n_, hipStream_t st, int n1 = 0) {
+        if (!n_) return;
+        tm.span(2, st, [&] {
+            if (n1 > 0) launch_big(R, off, n1, st);
+            if (n_ > n1) launch_big(R, off + n1, n_ - n1, st);
+        });
+        stats.n_schur_launches++;
+        stats.n_schur_big_launches++;
+    }
+    void schur_small(const LevelRange &R, int off, int n_, hipStream_t st) {
+        if (!n_) return;
+        tm.span(3, st, [&] { launch_small(R, off, n_, st); });
+        stats.n_schur_launches++;
+    }
+
+    // Level L of a 2D grid: the exchanges on the comm stream C, the panels in
+    // R.nch chunks.  P: TRSM(c) -> pack(c) -> [C: send / receive chunk c] for
+    // every c, so chunk c + 1's TRSM runs beside chunk c's transfer; the
+    // critical tiles of chunk c (P) and its rest tiles (Schur stream) start
+    // when chunk c is in.
+    void level_chunked(size_t L, double thresh) {
+        const LevelRange &R = levels[L];
+        hipStream_t P = pstream, C = cstream;
+        diag_step(R, thresh, P);
+        auto exchange = [&](const vector<Sec> &secs, int off, int cnt, const char *what, hipEvent_t done) {
+            HIPCHK(hipEventRecord(ev_pk, P));
+            HIPCHK(hipStreamWaitEvent(C, ev_pk, 0));
+            X.s = C;
+            if (cnt) tm.span(4, C, [&] { issue(secs, off, cnt, what, (int)L, d_dpk.p, d_pan.p); });
+            HIPCHK(hipEventRecord(done, C));
+        };
+        if (R.dc_n || R.ds_n) {
+            if (R.dc_n) tm.span(4, P, [&] { pack_diag(R, P); });
+            exchange(dsecs, R.ds_off, R.ds_n, "diagonal-package exchange", ev_dx);
+            HIPCHK(hipStreamWaitEvent(P, ev_dx, 0));
         }
-        try {
-            sync();
-        } catch (...) {
-            if (d2h.joinable()) d2h.join();
-            throw;
+        for (int ch = 0; ch < R.nch; ++ch) {
+            if (R.lf_o[ch + 1] > R.lf_o[ch] || R.uf_o[ch + 1] > R.uf_o[ch])
+                tm.span(1, P, [&] { launch_trsm_fast(R, P, ch); });
+            if (ch == 0) trsm_generic(R, P); // (wide supernodes' generic items: all in chunk 0)
+            const int pcn = R.pc_o[ch + 1] - R.pc_o[ch];
+            if (pcn) tm.span(4, P, [&] { pack_panels(R.pc_off + R.pc_o[ch], pcn, P); });
+            exchange(psecs, R.ps_off + R.ps_o[ch], R.ps_o[ch + 1] - R.ps_o[ch], "L/U panel exchange",
+                     ev_cx[ch]);
         }
-        if (overlap_dl) {
-            const auto t1 = std::chrono::steady_clock::now();
-            d2h.join();
-            SLU_REQUIRE(d2h_err.empty(), "factor download: %s", d2h_err.c_str());
-            stats.t_d2h_tail_ms = ms_since(t1);
-            stats.t_d2h_ms = d2h_ms;
-            stats.d2h_bytes = dbytes;
-            stats.n_d2h_copies = ncopies;
+        // critical tiles of L on the panel stream, after the rest of L-1
+        if (L > 0) HIPCHK(hipStreamWaitEvent(P, ev_rest[L - 1], 0));
+        for (int ch = 0; ch < R.nch; ++ch) {
+            HIPCHK(hipStreamWaitEvent(P, ev_cx[ch], 0));
+            schur_big(R, R.big_off + R.bc_o[ch], R.bc_o[ch + 1] - R.bc_o[ch], P);
+            schur_small(R, R.tile_off + R.sc_o[ch], R.sc_o[ch + 1] - R.sc_o[ch], P);
         }
-        host_current = overlap_dl;
+        HIPCHK(hipEventRecord(ev_pan[L], P));
+        // the rest of L on the Schur stream, chunk by chunk as they arrive
+        for (int ch = 0; ch < R.nch; ++ch) {
+            HIPCHK(hipStreamWaitEvent(stream, ev_cx[ch], 0));
+            schur_big(R, R.big_off + R.bigc_n + R.br_o[ch], R.br_o[ch + 1] - R.br_o[ch], stream);
+            schur_small(R, R.tile_off + R.tilec_n + R.sr_o[ch], R.sr_o[ch + 1] - R.sr_o[ch], stream);
+        }
+    }
+
+    // Level L of one rank alone, or of a grid in serial mode: look-ahead of
+    // one level on two streams:
+    //   pstream: panel(L) -> [wait rest(L-1)] -> critical tiles(L) -> panel(L+1) ...
+    //   stream : [wait panel(L)] -> rest tiles(L) -> [rest(L) done] ...
+    // Critical tiles update exactly the destinations in the panels of
+    // level L+1, so panel(L+1) (diag LU, TRSM, exchanges) runs beside the
+    // bulk of level L's Schur update (SRC/pdgstrf.c:1115-1356 look-ahead).
+    void level_plain(size_t L, double thresh) {
+        const LevelRange &R = levels[L];
+        hipStream_t P = opts.serial ? stream : pstream;
+        diag_step(R, thresh, P);
+        if (R.dc_n || R.ds_n)
+            tm.span(4, P, [&] {
+                pack_diag(R, P);
+                issue(dsecs, R.ds_off, R.ds_n, "diagonal-package exchange", (int)L, d_dpk.p, d_pan.p);
+            });
+        if (R.lf_n || R.uf_n) tm.span(1, P, [&] { launch_trsm_fast(R, P); });
+        trsm_generic(R, P);
+        if (R.pc_n || R.ps_n)
+            tm.span(4, P, [&] {
+                pack_panels(R.pc_off, R.pc_n, P);
+                issue(psecs, R.ps_off, R.ps_n, "L/U panel exchange", (int)L, d_dpk.p, d_pan.p);
+            });
+        HIPCHK(hipEventRecord(ev_pan[L], P));
+        // critical tiles of L on the panel stream, after the rest of L-1
+        if (L > 0) HIPCHK(hipStreamWaitEvent(P, ev_rest[L - 1], 0));
+        schur_big(R, R.big_off, R.bigc_n, P);
+        schur_small(R, R.tile_off, R.tilec_n, P);
+        // the rest of L on the Schur stream, once the panels of L exist;
+        // the first rest_split %% of the big rest tiles as a launch of their own
+        HIPCHK(hipStreamWaitEvent(stream, ev_pan[L], 0));
+        const int nrest = R.big_n - R.bigc_n;
+        const int n1 = rest_split > 0 && !opts.serial ? (int)((i64)nrest * rest_split / 100) : 0;
+        schur_big(R, R.big_off + R.bigc_n, nrest, stream, n1);
+        schur_small(R, R.tile_off + R.tilec_n, R.tile_n - R.tilec_n, stream);
+    }
+
+    // info and the tiny-pivot count of the factorization just synchronised
+    void collect_info(int *info, int *tiny) {
         int hc[4];
         HIPCHK(hipMemcpy(hc, d_counters.p, sizeof hc, hipMemcpyDeviceToHost));
         SLU_REQUIRE(hc[1] == 0, "factor: a diagonal-block strip waited more than a second for its left "
@@ -3475,54 +2934,18 @@ struct Plan : PlanBase {
         }
         *info = my_info;
         *tiny = hc[0];
-        if (timing) {
-            float ms;
-            HIPCHK(hipEventElapsedTime(&ms, ev[e_start], ev[e_end]));
-            stats.t_total_ms = ms;
-            stats.t_diag_ms = stats.t_trsm_ms = stats.t_schur_ms = stats.t_schur_big_ms = 0;
-            stats.t_comm_ms = 0;
-            stats.schur_big_flops = 0;
-            for (auto &s : spans) {
-                HIPCHK(hipEventElapsedTime(&ms, ev[s.a], ev[s.b]));
-                if (s.kind == 0) stats.t_diag_ms += ms;
-                else if (s.kind == 1) stats.t_trsm_ms += ms;
-                else if (s.kind == 4) stats.t_comm_ms += ms;
-                else {
-                    stats.t_schur_ms += ms;
-                    if (s.kind == 2) stats.t_schur_big_ms += ms;
-                }
-            }
-            for (auto &R : levels) stats.schur_big_flops += R.big_flops;
-            for (int i = 0; i < 8; ++i) stats.t_phase_ms[i] = 0;
-            stats.t_zreduce_ms = 0;
-            for (size_t i = 0; i < zmarks.size() && i < 8; ++i) {
-                HIPCHK(hipEventElapsedTime(&ms, ev[zmarks[i][0]], ev[zmarks[i][1]]));
-                stats.t_phase_ms[i] = ms;
-                HIPCHK(hipEventElapsedTime(&ms, ev[zmarks[i][1]], ev[zmarks[i][2]]));
-                stats.t_zreduce_ms += ms;
-            }
-            if (opts.timing >= 2) { // per-level breakdown (stderr)
-                vector<std::array<double, 5>> t(levels.size(), {0, 0, 0, 0, 0});
-                for (auto &s : spans) {
-                    HIPCHK(hipEventElapsedTime(&ms, ev[s.a], ev[s.b]));
-                    t[s.level][s.kind] += ms;
-                }
-                fprintf(stderr, "[slu rank %d] lvl nsup diag trsm big small atomic  GFLOP  diag_ms trsm_ms big_ms small_ms comm_ms  TF/s wall_ms\n", iam);
-                for (size_t L = 0; L < levels.size(); ++L) {
-                    const LevelRange &R = levels[L];
-                    double sch = t[L][2] + t[L][3];
-                    float wall = 0;
-                    HIPCHK(hipEventElapsedTime(&wall, ev[L ? lvl_end[L - 1] : e_start], ev[lvl_end[L]]));
-                    fprintf(stderr, "[slu rank %d] %3zu %5zu %4d %5d %5d %5d %6d %7.2f %8.3f %7.3f %7.3f %7.3f %7.3f %6.2f %7.3f\n",
-                            iam, L, bylev[L].size(), R.diag_n + R.df_n, R.lf_n + R.uf_n + R.tl_n + R.tu_n,
-                            R.big_n, R.tile_n, R.atomic_tiles, R.schur_flops / 1e9, t[L][0], t[L][1], t[L][2], t[L][3],
-                            t[L][4], sch > 0 ? R.schur_flops / sch / 1e9 : 0.0, (double)wall);
-                }
-            }
-            for (auto e : ev) (void)hipEventDestroy(e);
-        }
+    }
+
+    // diagnostics build (SLU_SB_STAMP): per-tile stamps of k_schur_big, to SLU_STAMP_OUT
+    void stamp_reset() {
 #ifdef SLU_SB_STAMP
-        if (const char *fn = getenv("SLU_STAMP_OUT")) { // diagnostics build: per-tile stamps
+        const unsigned z = 0;
+        HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(slu_stamp_n), &z, sizeof z));
+#endif
+    }
+    void stamp_dump() {
+#ifdef SLU_SB_STAMP
+        if (const char *fn = getenv("SLU_STAMP_OUT")) {
             unsigned cnt = 0;
             HIPCHK(hipMemcpyFromSymbol(&cnt, HIP_SYMBOL(slu_stamp_n), sizeof cnt));
             cnt = std::min(cnt, SLU_STAMP_MAX);
@@ -3534,6 +2957,105 @@ struct Plan : PlanBase {
             }
         }
 #endif
+    }
+
+    void factor(double anorm, int *info, int *tiny) override {
+        SLU_REQUIRE(vstate == 1, "factor: no unfactored values on the device (%s)",
+                    vstate == 2 ? "already factored; upload / restore / fill_a first"
+                                : "upload or fill_a first");
+        vstate = 2;
+        a_fact = d_acur;
+        // thresh = smach_dist("Epsilon") * anorm (SRC/pdgstrf.c:412-413); in
+        // psgstrf thresh is a float product.
+        const float s_eps = 5.9604644775390625e-08f; // FLT_EPSILON * 0.5
+        double thresh = sizeof(T) == 4 ? (double)(float)(s_eps * (float)anorm) : (double)s_eps * anorm;
+        HIPCHK(hipMemsetAsync(d_counters.p, 0, d_counters.bytes(), stream));
+        if (++ds_epoch >= 0x7fffffffu) { // (strip flags: a new epoch per factorization)
+            HIPCHK(hipMemsetAsync(d_dsflags.p, 0, d_dsflags.bytes(), stream));
+            ds_epoch = 1;
+        }
+        HIPCHK(hipMemsetAsync(d_zpiv.p, 0, d_zpiv.bytes(), stream));
+        stamp_reset();
+        tm.reset(opts.timing);
+        if (zmode) { // ancestor forests another layer factors start from zero
+            launch_zranges(zr_off[0], zr_off[1], ZR_ZERO, stream);
+            zbytes = 0;
+        }
+        tm.start(stream);
+        HIPCHK(hipEventRecord(ev_start, stream));
+        HIPCHK(hipStreamWaitEvent(pstream, ev_start, 0));
+        X.s = opts.serial ? stream : pstream;
+        stats.n_schur_launches = 0;
+        stats.n_schur_big_launches = 0;
+        std::fill(path_counts, path_counts + PC_N, 0);
+        path_counts[PC_KSPLIT_KINFOS] = n_ksplit_kinfos;
+        // 3D grids: my phases one after the other, each followed by its
+        // ancestor reduction (SRC/pdgstrf3d.c:300-345)
+        const int nph = zmode ? my_last + 1 : 1;
+        int last_L = -1;
+        for (int ph = 0; ph < nph; ++ph) {
+            const size_t L0 = zmode ? phase_lv[ph] : 0, L1 = zmode ? phase_lv[ph + 1] : levels.size();
+            for (size_t L = L0; L < L1; ++L) {
+                tm.level((int)L);
+                last_L = (int)L;
+                if (xmode && !opts.serial) level_chunked(L, thresh);
+                else level_plain(L, thresh);
+                HIPCHK(hipEventRecord(ev_rest[L], stream));
+                tm.level_end(stream); // level wall time
+            }
+            if (zmode) {
+                hipStream_t P = opts.serial ? stream : pstream;
+                if (last_L >= 0) HIPCHK(hipStreamWaitEvent(P, ev_rest[last_L], 0));
+                tm.phase_end(P);
+                if (ph < maxlvl - 1) {
+                    tm.span(4, P, [&] { zreduce(ph, P); });
+                    HIPCHK(hipEventRecord(ev_pend, P));
+                    HIPCHK(hipStreamWaitEvent(stream, ev_pend, 0));
+                }
+                tm.reduce_end(P);
+            }
+        }
+        if (xmode && !opts.serial) { // the comm stream's last group before the end of the factorization
+            HIPCHK(hipEventRecord(ev_pend, cstream));
+            HIPCHK(hipStreamWaitEvent(stream, ev_pend, 0));
+        }
+        X.s = opts.serial ? stream : pstream;
+        HIPCHK(hipEventRecord(ev_pend, pstream));
+        HIPCHK(hipStreamWaitEvent(stream, ev_pend, 0));
+        HIPCHK(hipGetLastError());
+        tm.end(stream);
+        double d2h_ms = 0;
+        int64_t ncopies = 0;
+        double dbytes = 0;
+        const bool overlap_dl = opts.overlap_download != 0;
+        // diagnostics: SLU_D2H_AFTER=1 starts the D2H only after the device
+        // finished the factorization (no overlap, same copy path)
+        const bool d2h_after = overlap_dl && getenv("SLU_D2H_AFTER");
+        if (d2h_after) sync();
+        HelperThread dl; // (after the locals it writes: joined before they go, on every path)
+        if (overlap_dl)
+            dl.start(device(), [&] {
+                const auto t0 = std::chrono::steady_clock::now();
+                try {
+                    run_d2h(dbytes, ncopies);
+                } catch (const std::exception &e) {
+                    throw Error(std::string("factor download: ") + e.what());
+                }
+                d2h_ms = ms_since(t0);
+            });
+        sync();
+        if (overlap_dl) {
+            const auto t1 = std::chrono::steady_clock::now();
+            dl.join();
+            stats.t_d2h_tail_ms = ms_since(t1);
+            stats.t_d2h_ms = d2h_ms;
+            stats.d2h_bytes = dbytes;
+            stats.n_d2h_copies = ncopies;
+        }
+        host_current = overlap_dl;
+        collect_info(info, tiny);
+        tm.finish(stats, levels, bylev, iam);
+        stamp_dump();
     }
 
     // ------------------------------------------------------- device solve
@@ -3783,11 +3305,7 @@ struct Plan : PlanBase {
             T *buf = mycol == r.c ? xv + xsup[r.k] : (mycol == own_c ? d_sv_slot.p + r.slot : nullptr);
             X.section(G_ROW, r.c, 1u << own_c, buf, (size_t)W(r.k) * sizeof(T));
         }
-        X.phase = "solve: partial sums to the diagonal owners";
-        X.level = L;
-        X.flush();
-        X.phase = "plan-time exchange";
-        X.level = -1;
+        X.flush_as("solve: partial sums to the diagonal owners", L);
         const int na = sv_add_off[L + 1] - sv_add_off[L];
         if (na)
             hipLaunchKernelGGL(k_sv_add<T>, dim3(na), dim3(256), 0, stream, d_sv_add.p + sv_add_off[L],
@@ -4219,6 +3737,12 @@ struct Plan : PlanBase {
         (void)hipEventDestroy(e1);
         stats.t_fill_ms = ms;
     }
+
+    // ---- helper threads of the plan build: the H2D copy of the values and
+    // the pinned-slot allocation.  Declared last: they use the DevBuf members
+    // above, and members are destroyed in reverse order, so the threads are
+    // joined before any buffer is freed (also when the constructor throws).
+    HelperThread up_thread, pin_thread;
 };
 
 template <typename P> PlanBase *make_plan(void *LU, int n, int pr, int pc, int iam, slu_comm *c,
@@ -4226,966 +3750,9 @@ template <typename P> PlanBase *make_plan(void *LU, int n, int pr, int pc, int i
     return new P((decltype(std::declval<P>().LU))LU, n, pr, pc, iam, c, o);
 }
 
-
-// ---------------------------------------------------------------- amalgamation
-// A 1x1 plan over the coarse partition of csrc/amalg.h.  The inner plan is an
-// ordinary Plan built on the coarse LUstruct's index arrays (held here, no
-// host values); the caller's values travel in their own layout (d_oL / d_oU)
-// and are relaid on the device: expand at upload (caller -> coarse), compress
-// at download (coarse -> caller).  The device-resident state between upload
-// and download -- what factor(), snapshot / restore, fill_a, solve and refine
-// work on -- is the coarse layout.
-template <typename T, typename HT, typename LocalLU, typename LUS>
-struct AmalgPlan : PlanBase {
-    using Inner = Plan<T, HT, LocalLU, LUS>;
-    LUS *LU = nullptr;
-    int n = 0, ns = 0;
-    Amalg A;
-    // the coarse LUstruct the inner plan reads (index arrays only)
-    LUS mlu{};
-    LocalLU mllu{};
-    Glu_persist_t mglu{};
-    vector<int_t *> mlidx, muidx;
-    std::unique_ptr<Inner> in;
-    slu_engine_opts opts{};
-    // caller layout on the device, and the relayout programs
-    DevBuf<T> d_oL, d_oU;
-    DevBuf<LColX> d_lx;
-    DevBuf<int32_t> d_lrow, d_ucd;
-    DevBuf<uint16_t> d_ucl;
-    DevBuf<UChunk> d_ur;
-    DevBuf<i64> d_D;
-    vector<i64> usrc; // caller U value offset per block row
-    std::thread up_thread;
-    std::string up_err;
-    // the coarse L / U storage, allocated beside the analysis as soon as its
-    // sizes are known (after pass 3a), adopted by the inner plan
-    DevBuf<T> pre[2];
-    std::thread alloc_thread;
-    std::string alloc_err;
-    std::mutex o_mu; // ensure_o: the upload thread or the D2H program build
-    // fresh HBM is mapped at its first touch; the caller-layout buffers are
-    // touched first thing on the upload thread (o_mapped), and the D2H warm-up
-    // (pinned slots) waits for that
-    std::mutex map_mu;
-    std::condition_variable map_cv;
-    bool o_mapped = false;
-    double t_omap = 0;
-    std::chrono::steady_clock::time_point t_born = std::chrono::steady_clock::now();
-    void set_mapped() {
-        std::lock_guard<std::mutex> lk(map_mu);
-        o_mapped = true;
-        map_cv.notify_all();
-    }
-    // the D2H's pinned slots and HBM staging slots, allocated and touched
-    // (one DMA through each) beside the plan build: lazily, the first
-    // factorization paid ~70 ms more D2H tail for them
-    std::thread warm_thread;
-    std::string warm_err;
-    DevBuf<char> warm_stage;
-    void warm_join() {
-        if (warm_thread.joinable()) warm_thread.join();
-        SLU_REQUIRE(warm_err.empty(), "%s", warm_err.c_str());
-    }
-    double up_ms = 0, h2d_bytes = 0;
-    double t_amalg = 0, t_plan = 0, t_expand = 0, t_compress = 0, t_d2h = 0;
-    bool coarse_current = false; // d_oL / d_oU stale: the coarse storage holds newer values
-
-    static double ms_since(std::chrono::steady_clock::time_point t0) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0)
-            .count();
-    }
-
-    // Returns nullptr when nothing merges (the caller then builds a Plan).
-    static AmalgPlan *make(LUS *lu, int n_, const slu_engine_opts *o, double zero_frac, int maxw) {
-        auto t0 = std::chrono::steady_clock::now();
-        std::unique_ptr<AmalgPlan> P(new AmalgPlan);
-        P->LU = lu;
-        P->n = n_;
-        if (o) P->opts = *o;
-        const int_t *xsup = lu->Glu_persist->xsup;
-        P->ns = (int)(lu->Glu_persist->supno[n_ - 1] + 1);
-        LocalLU *L = lu->Llu;
-        const int ns = P->ns;
-        // caller value layout: contiguous per block column / row in supernode order
-        i64 lv = 0, uv = 0;
-        P->usrc.assign(ns + 1, 0);
-        for (int s = 0; s < ns; ++s) {
-            if (L->Lrowind_bc_ptr[s]) lv += (i64)L->Lrowind_bc_ptr[s][1] * (xsup[s + 1] - xsup[s]);
-            if (L->Ufstnz_br_ptr[s]) uv += L->Ufstnz_br_ptr[s][1];
-            P->usrc[s + 1] = uv;
-        }
-        const bool prof = getenv("SLU_PROFILE_PLAN") != nullptr;
-        auto tk = t0;
-        auto tick = [&](const char *what) { // SLU_PROFILE_PLAN: phase times on stderr
-            if (!prof) return;
-            fprintf(stderr, "[slu amalg plan] %-22s %7.1f ms\n", what, ms_since(tk));
-            tk = std::chrono::steady_clock::now();
-        };
-        HIPCHK(hipSetDevice(0));
-        tick("caller layout");
-        P->o_lv = lv;
-        P->o_uv = uv;
-        // the caller-layout copies only where values cross PCIe: a plan fed
-        // by fill_a and read by solve never allocates them (the upload thread
-        // allocates them itself, beside the analysis)
-        if (!P->opts.overlap_upload && P->opts.overlap_download) P->ensure_o();
-        tick("caller-layout alloc");
-        P->A.on_sizes = [raw = P.get()](int64_t lv2, int64_t uv2) {
-            raw->alloc_thread = std::thread([raw, lv2, uv2] {
-                try {
-                    HIPCHK(hipSetDevice(0));
-                    const auto ta = std::chrono::steady_clock::now();
-                    const double at = ms_since(raw->t_born);
-                    raw->pre[0].alloc_guarded(std::max<i64>(lv2, 1), SB_UGUARD);
-                    raw->pre[1].alloc_guarded(std::max<i64>(uv2, 1), SB_UGUARD);
-                    if (getenv("SLU_PROFILE_PLAN"))
-                        fprintf(stderr, "[slu amalg plan]   (coarse storage %.1f GB mapped in %.1f ms, from %.1f ms)\n",
-                                (lv2 + uv2) * sizeof(T) / 1e9, ms_since(ta), at);
-                } catch (const std::exception &e) {
-                    raw->alloc_err = e.what();
-                }
-            });
-        };
-        if (P->opts.overlap_upload) {
-            AmalgPlan *raw = P.get();
-            P->up_thread = std::thread([raw] {
-                try {
-                    HIPCHK(hipSetDevice(0));
-                    raw->h2d();
-                } catch (const std::exception &e) {
-                    raw->up_err = e.what();
-                }
-                raw->set_mapped(); // (also on failure: the warm-up waits for it)
-            });
-        }
-        if (P->opts.overlap_download) {
-            AmalgPlan *raw = P.get();
-            raw->warm_thread = std::thread([raw] {
-                try {
-                    HIPCHK(hipSetDevice(0));
-                    // after the caller-layout buffers' mapping: beside it the
-                    // pinned allocation made that mapping 102-274 instead of
-                    // 34-37 ms (profiles/r04y)
-                    if (raw->opts.overlap_upload) {
-                        std::unique_lock<std::mutex> lk(raw->map_mu);
-                        raw->map_cv.wait(lk, [raw] { return raw->o_mapped; });
-                    }
-                    i64 slot = 128ll << 20; // (Plan::D2H_SLOT, and its override as in build_d2h)
-                    if (const char *e = getenv("SLU_D2H_SLOT_KB")) slot = std::max<i64>(16, atoll(e)) << 10;
-                    constexpr int NS = Inner::D2H_NS;
-                    std::lock_guard<std::mutex> in_use(pinned_pool(1).use);
-                    std::vector<char *> slots = pinned_pool(1).get(NS, slot);
-                    raw->warm_stage.alloc((size_t)NS * slot);
-                    hipStream_t st = nullptr;
-                    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-                    HIPCHK(hipMemsetAsync(raw->warm_stage.p, 0, raw->warm_stage.bytes(), st));
-                    for (int i = 0; i < NS; ++i)
-                        HIPCHK(hipMemcpyAsync(slots[i], raw->warm_stage.p + (i64)i * slot, (size_t)slot,
-                                              hipMemcpyDeviceToHost, st));
-                    HIPCHK(hipStreamSynchronize(st));
-                    HIPCHK(hipStreamDestroy(st));
-                } catch (const std::exception &e) {
-                    raw->warm_err = e.what();
-                }
-            });
-        }
-        try {
-            vector<const int_t *> li(L->Lrowind_bc_ptr, L->Lrowind_bc_ptr + ns),
-                ui(L->Ufstnz_br_ptr, L->Ufstnz_br_ptr + ns);
-            const auto ta = std::chrono::steady_clock::now();
-            P->A.defer_programs = true;
-            if (!P->A.build(n_, ns, xsup, li.data(), ui.data(), zero_frac, maxw)) {
-                if (P->up_thread.joinable()) P->up_thread.join();
-                if (P->alloc_thread.joinable()) P->alloc_thread.join();
-                if (P->warm_thread.joinable()) P->warm_thread.join();
-                return nullptr;
-            }
-            SLU_REQUIRE(P->A.lval1 == lv && P->A.uval1 == uv, "amalgamation: value counts");
-            P->t_amalg = ms_since(ta);
-            tick("analysis");
-            // the relayout programs (host pass 4; beside the coarse plan's
-            // build it only slowed both down on the box's 16 cores).  Only an
-            // upload or a download of the caller-layout values runs them: a
-            // plan fed by fill_a whose factors stay in HBM (the device-
-            // resident drop-in) builds them when one first happens
-            const bool progs_now = P->opts.overlap_upload || P->opts.overlap_download;
-            if (progs_now) {
-                P->A.build_programs();
-                tick("programs (host)");
-            }
-            P->build_inner();
-            tick("coarse plan");
-            if (progs_now) {
-                P->build_programs();
-                P->progs = true;
-                tick("relayout programs");
-            }
-            if (P->opts.overlap_download) P->build_d2h();
-            tick("d2h programs");
-        } catch (...) {
-            if (P->up_thread.joinable()) P->up_thread.join();
-            if (P->alloc_thread.joinable()) P->alloc_thread.join();
-            if (P->prog_thread.joinable()) P->prog_thread.join();
-            if (P->warm_thread.joinable()) P->warm_thread.join();
-            throw;
-        }
-        P->t_plan = ms_since(t0);
-        P->sync_stats();
-        return P.release();
-    }
-
-    void build_inner() {
-        const int ns2 = A.ns2;
-        mlidx.assign(ns2, nullptr);
-        muidx.assign(ns2, nullptr);
-        for (int J = 0; J < ns2; ++J) {
-            if (A.Loff2[J] >= 0) mlidx[J] = A.Lidx2.data() + A.Loff2[J];
-            if (A.Uoff2[J] >= 0) muidx[J] = A.Uidx2.data() + A.Uoff2[J];
-        }
-        mglu.xsup = A.xsup2.data();
-        mglu.supno = A.supno2.data();
-        mllu.Lrowind_bc_ptr = mlidx.data();
-        mllu.Ufstnz_br_ptr = muidx.data();
-        mlu.Glu_persist = &mglu;
-        mlu.Llu = &mllu;
-        slu_engine_opts io = opts;
-        io.overlap_upload = io.overlap_download = 0;
-        const auto tj = std::chrono::steady_clock::now();
-        if (alloc_thread.joinable()) alloc_thread.join();
-        if (getenv("SLU_PROFILE_PLAN"))
-            fprintf(stderr, "[slu amalg plan]   (coarse storage: waited %.1f ms)\n", ms_since(tj));
-        SLU_REQUIRE(alloc_err.empty(), "%s", alloc_err.c_str());
-        in.reset(new Inner(&mlu, n, 1, 1, 0, nullptr, &io, pre));
-    }
-
-    // Programs in level order of the coarse plan (so the D2H can compress a
-    // level as soon as its panels are done): lx / ublks items of the groups
-    // of level L at [lx_lev[L], lx_lev[L+1]) / [ub_lev[L], ub_lev[L+1]).
-    vector<int> lx_lev, ub_lev; // (ub_lev: U chunks)
-    bool progs = false;         // the relayout programs are built
-    void ensure_programs() {
-        if (progs) return;
-        // (the index pointer tables of the LUstruct as it is now: those
-        // make() had are gone; the structure is the plan's by the cache key)
-        LocalLU *L = LU->Llu;
-        const vector<const int_t *> li(L->Lrowind_bc_ptr, L->Lrowind_bc_ptr + ns),
-            ui(L->Ufstnz_br_ptr, L->Ufstnz_br_ptr + ns);
-        A.set_index(li.data(), ui.data());
-        A.build_programs();
-        build_programs();
-        progs = true;
-    }
-    void build_programs() {
-        const int nl = (int)in->levels.size();
-        auto lev = [&](int s) { return in->level_of[A.grp[s]]; };
-        // L: column ranges of <= 64 K values per workgroup
-        vector<vector<LColX>> bl(nl);
-        for (int s = 0; s < ns; ++s) {
-            const Amalg::LCol &C = A.lcols[s];
-            if (!C.nsupr) continue;
-            const int cpi = std::max(1, (int)(65536 / C.nsupr));
-            for (int c0 = 0; c0 < C.w; c0 += cpi)
-                bl[lev(s)].push_back({C.src, C.dst, C.map, C.nsupr, c0, std::min(C.w, c0 + cpi), C.ld2});
-        }
-        vector<LColX> lx;
-        lx_lev.assign(nl + 1, 0);
-        for (int L = 0; L < nl; ++L) {
-            lx.insert(lx.end(), bl[L].begin(), bl[L].end());
-            lx_lev[L + 1] = (int)lx.size();
-        }
-        // U: the original block rows in level order, in chunks of <= 64
-        // non-empty columns (chunk counts in order, then the rows in parallel)
-        ur_h.clear();
-        {
-            vector<vector<int>> rows(nl);
-            for (int s = 0; s < ns; ++s)
-                if (A.urows[s].nc) rows[lev(s)].push_back(s);
-            vector<int> order;
-            order.reserve(ns);
-            vector<i64> first(ns + 1, 0);
-            ub_lev.assign(nl + 1, 0);
-            i64 nch = 0;
-            for (int L = 0; L < nl; ++L) {
-                for (int s : rows[L]) {
-                    first[order.size()] = nch;
-                    order.push_back(s);
-                    nch += (A.urows[s].nc + 63) / 64;
-                }
-                ub_lev[L + 1] = (int)nch;
-            }
-            ur_h.resize(nch);
-            parallel_for((int)order.size(), [&](int i) {
-                const Amalg::URowX &R = A.urows[order[i]];
-                i64 src = R.src, k = first[i];
-                for (int c0 = 0; c0 < R.nc; c0 += 64) {
-                    const int nc = std::min(64, R.nc - c0);
-                    ur_h[k++] = {src, R.c0 + c0, nc, R.end};
-                    for (int c = c0; c < c0 + nc; ++c) src += A.ucl[R.c0 + c] + 1;
-                }
-            }, 256);
-        }
-        nlx = (int)lx.size();
-        if (lx.empty()) lx.push_back({0, 0, 0, 0, 0, 0, 0});
-        if (ur_h.empty()) ur_h.resize(1);
-        lx_h = std::move(lx);
-        // the tables go up on a helper thread (1.5 GB at 100^3): the first
-        // relayout joins it (programs_ready)
-        prog_thread = std::thread([this] {
-            try {
-                HIPCHK(hipSetDevice(0));
-                auto up = [](auto &d, const auto &h) { // (a 1-element buffer for an empty table)
-                    if (h.empty()) d.alloc(1);
-                    else d.upload(h.data(), h.size());
-                };
-                up(d_lx, lx_h);
-                up(d_ur, ur_h);
-                up(d_lrow, A.lrow);
-                up(d_ucd, A.ucd);
-                up(d_ucl, A.ucl);
-                up(d_D, A.D);
-            } catch (const std::exception &e) {
-                prog_err = e.what();
-            }
-        });
-    }
-    vector<LColX> lx_h;
-    vector<UChunk> ur_h;
-    std::thread prog_thread;
-    std::string prog_err;
-    std::mutex prog_mu;
-    void programs_ready() {
-        std::lock_guard<std::mutex> lk(prog_mu);
-        if (prog_thread.joinable()) prog_thread.join();
-        SLU_REQUIRE(prog_err.empty(), "%s", prog_err.c_str());
-    }
-    int nlx = 0;
-
-    // levels [L0, L1) of the relayout on stream st
-    void relayout_levels(int dir, int L0, int L1, hipStream_t st) {
-        ensure_programs();
-        programs_ready();
-        const int a = lx_lev[L0], b = lx_lev[L1];
-        if (b > a)
-            hipLaunchKernelGGL((k_amalg_l<T>), dim3(b - a), dim3(256), 0, st, d_lx.p + a, d_lrow.p,
-                               d_oL.p, in->d_L.p, dir);
-        const int u0 = ub_lev[L0], nr = ub_lev[L1] - u0;
-        if (nr > 0)
-            hipLaunchKernelGGL((k_amalg_u<T>), dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, st,
-                               d_ur.p + u0, nr, d_ucd.p, d_ucl.p, d_D.p, (i64)A.DL0, d_oU.p, in->d_L.p,
-                               in->d_U.p, dir);
-        HIPCHK(hipGetLastError());
-    }
-
-    // The overlapped D2H of the drop-in path (opts.overlap_download): the
-    // inner plan's pinned-slot pipeline (run_d2h) with fills that carry the
-    // caller's layout: a coarse group's members are consecutive supernodes,
-    // so its values are one range of d_oL and one of d_oU; before a fill is
-    // pushed, d2h_pre compresses every level up to the fill's into d_oL /
-    // d_oU on the D2H stream.
-    int compressed_to = 0;
-    void build_d2h() {
-        ensure_o(); // (the push programs address d_oL / d_oU)
-        Inner &P = *in;
-        warm_join();
-        if (warm_stage.p) P.d_stage.swap(warm_stage);
-        LocalLU *Llu = LU->Llu;
-        const int_t *xsup = LU->Glu_persist->xsup;
-        const int nl = (int)P.levels.size();
-        if (const char *e = getenv("SLU_D2H_SLOT_KB")) { // as the plain plan
-            P.D2H_SLOT = std::max<i64>(16, atoll(e)) << 10;
-            P.D2H_MIN = P.D2H_SLOT / 4;
-        }
-        vector<i64> lsrc(ns + 1, 0);
-        for (int s = 0; s < ns; ++s)
-            lsrc[s + 1] = lsrc[s] + (Llu->Lrowind_bc_ptr[s] ? (i64)Llu->Lrowind_bc_ptr[s][1] * (xsup[s + 1] - xsup[s]) : 0);
-        vector<int> g0(A.ns2 + 1, ns); // first original supernode of each group
-        for (int s = ns - 1; s >= 0; --s) g0[A.grp[s]] = s;
-        i64 fb = 0;
-        int seg0 = 0, hs0 = 0;
-        const i64 SLOT = P.D2H_SLOT, PIECE = Inner::D2H_PIECE;
-        auto close = [&](int L) {
-            if (fb == 0) return;
-            P.d2h_fills.push_back({L, seg0, (int)P.h_push.size() - seg0, hs0, (int)P.h_unpack.size() - hs0, fb});
-            seg0 = (int)P.h_push.size();
-            hs0 = (int)P.h_unpack.size();
-            fb = 0;
-        };
-        auto add = [&](const char *dev, char *host, i64 bytes, int L) {
-            i64 done = 0;
-            while (done < bytes) {
-                const i64 take = std::min(bytes - done, SLOT - fb);
-                for (i64 o = 0; o < take; o += PIECE)
-                    P.h_push.push_back({dev + done + o, fb + o, (int)std::min(PIECE, take - o)});
-                for (i64 o = 0; o < take; o += 4 * PIECE)
-                    P.h_unpack.push_back({host + done + o, fb + o, std::min(4 * PIECE, take - o)});
-                fb += (take + 15) & ~(i64)15;
-                done += take;
-                if (fb >= SLOT) close(L);
-            }
-        };
-        // one piece per group and factor where the caller's arrays are
-        // contiguous over the group's members (pddistribute's *_dat layout),
-        // else one per member
-        for (int L = 0; L < nl; ++L) {
-            for (int J : P.bylev[L]) {
-                for (int pass = 0; pass < 2; ++pass) {
-                    const vector<i64> &off = pass ? usrc : lsrc;
-                    const T *dbase = pass ? d_oU.p : d_oL.p;
-                    auto hptr = [&](int s) -> char * {
-                        if (pass) return Llu->Ufstnz_br_ptr[s] ? (char *)Llu->Unzval_br_ptr[s] : nullptr;
-                        return Llu->Lrowind_bc_ptr[s] ? (char *)Llu->Lnzval_bc_ptr[s] : nullptr;
-                    };
-                    int a = g0[J];
-                    while (a < g0[J + 1]) {
-                        int b = a;
-                        while (b < g0[J + 1] && (off[b + 1] == off[b] || !hptr(b))) ++b; // empty
-                        if (b == g0[J + 1]) break;
-                        char *h0 = hptr(b);
-                        int e = b + 1;
-                        while (e < g0[J + 1] && (off[e + 1] == off[e] ||
-                                                 hptr(e) == h0 + (off[e] - off[b]) * (i64)sizeof(T)))
-                            ++e;
-                        add((const char *)(dbase + off[b]), h0, (off[e] - off[b]) * (i64)sizeof(T), L);
-                        a = e;
-                    }
-                }
-            }
-            if (fb >= P.D2H_MIN || L + 1 == nl) close(L);
-        }
-        P.d_push.upload(P.h_push.empty() ? vector<PushSeg>(1) : P.h_push);
-        P.d2h_pre = [this](int L, hipStream_t st) {
-            if (L + 1 > compressed_to) {
-                relayout_levels(1, compressed_to, L + 1, st);
-                compressed_to = L + 1;
-            }
-        };
-        P.opts.overlap_download = 1;
-    }
-
-    i64 o_lv = 0, o_uv = 0;
-    void ensure_o() {
-        std::lock_guard<std::mutex> lk(o_mu);
-        if (d_oL.p) return;
-        d_oL.alloc(std::max<i64>(o_lv, 1));
-        d_oU.alloc(std::max<i64>(o_uv, 1));
-    }
-    // caller layout: host arrays <-> d_oL / d_oU
-    vector<Xfer> xfers() {
-        ensure_o();
-        LocalLU *L = LU->Llu;
-        vector<Xfer> xs;
-        const int_t *xsup = LU->Glu_persist->xsup;
-        i64 lo = 0;
-        for (int s = 0; s < ns; ++s) {
-            if (!L->Lrowind_bc_ptr[s]) continue;
-            const i64 cnt = (i64)L->Lrowind_bc_ptr[s][1] * (xsup[s + 1] - xsup[s]);
-            xs.push_back({(char *)(d_oL.p + lo), (char *)L->Lnzval_bc_ptr[s], (size_t)cnt * sizeof(T)});
-            lo += cnt;
-        }
-        for (int s = 0; s < ns; ++s)
-            if (L->Ufstnz_br_ptr[s])
-                xs.push_back({(char *)(d_oU.p + usrc[s]), (char *)L->Unzval_br_ptr[s],
-                              (size_t)(usrc[s + 1] - usrc[s]) * sizeof(T)});
-        return merge_xfers(std::move(xs));
-    }
-    void h2d() {
-        const auto t0 = std::chrono::steady_clock::now();
-        vector<Xfer> xs = xfers();
-        if (!o_mapped) {
-            hipStream_t st = nullptr;
-            HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            HIPCHK(hipMemsetAsync(d_oL.p, 0, sizeof(T), st));
-            HIPCHK(hipMemsetAsync(d_oU.p, 0, sizeof(T), st));
-            HIPCHK(hipStreamSynchronize(st));
-            HIPCHK(hipStreamDestroy(st));
-            t_omap = ms_since(t0);
-            if (getenv("SLU_PROFILE_PLAN"))
-                fprintf(stderr, "[slu amalg plan]   (caller-layout storage %.1f GB mapped in %.1f ms, at %.1f ms)\n",
-                        (d_oL.bytes() + d_oU.bytes()) / 1e9, t_omap, ms_since(t_born));
-            set_mapped();
-        }
-        staged_h2d(xs, 0);
-        h2d_bytes = 0;
-        for (auto &x : xs) h2d_bytes += (double)x.bytes;
-        up_ms = ms_since(t0);
-    }
-
-    void relayout(int dir) {
-        ensure_o();
-        hipStream_t st = in->stream;
-        if (dir == 0) {
-            HIPCHK(hipMemsetAsync(in->d_L.p, 0, in->d_L.bytes(), st));
-            HIPCHK(hipMemsetAsync(in->d_U.p, 0, in->d_U.bytes(), st));
-        }
-        relayout_levels(dir, 0, (int)in->levels.size(), st);
-        HIPCHK(hipStreamSynchronize(st));
-    }
-
-    void sync_stats() {
-        stats = in->stats;
-        std::copy(in->path_counts, in->path_counts + PlanBase::PC_N, this->path_counts);
-        // the caller's partition's algorithmic work (what the reference's
-        // pdgstrf does on this LUstruct); the coarse partition's own counts
-        // (explicit zeros included) stay in the kernel-level fields
-        // (schur_big_flops, schur_flops_padded)
-        const bool cp = sizeof(T) == 16;
-        stats.schur_flops = A.fl_schur * (cp ? 4.0 : 1.0);
-        stats.panel_flops = (cp ? 6 * A.fl_s1 + 10 * A.fl_w + 8 * A.fl_s2 : A.fl_s1 + 2 * A.fl_s2) +
-                            (cp ? 4.0 : 1.0) * A.fl_trsm + A.fl_trsv;
-        stats.nsupers_in = ns;
-        stats.amalg_groups = A.n_merged_groups;
-        stats.amalg_zeros = (double)A.zeros;
-        stats.t_amalg_ms = t_amalg;
-        stats.t_plan_ms = t_plan;
-        stats.t_upload_ms = up_ms;
-        stats.h2d_bytes = h2d_bytes;
-        stats.t_expand_ms = t_expand;
-        stats.t_compress_ms = t_compress;
-        stats.t_d2h_ms = t_d2h;
-        stats.d2h_bytes = (double)(d_oL.bytes() + d_oU.bytes());
-    }
-
-    void upload() override {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (up_thread.joinable()) {
-            up_thread.join();
-            if (!up_err.empty()) {
-                std::string e;
-                e.swap(up_err);
-                throw Error(e);
-            }
-        } else {
-            h2d();
-        }
-        const auto t1 = std::chrono::steady_clock::now();
-        relayout(0);
-        t_expand = ms_since(t1);
-        in->vstate = 1;
-        in->d_acur = nullptr;
-        in->host_current = false;
-        coarse_current = false;
-        host_done = false;
-        sync_stats();
-        stats.t_upload_wait_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    }
-    void adopt_factors() override {
-        upload();
-        in->sync();
-        in->vstate = 2;
-        coarse_current = true;
-        host_done = true; // the caller's arrays hold these factors already
-    }
-    void factor(double anorm, int *info, int *tiny) override {
-        compressed_to = 0;
-        in->factor(anorm, info, tiny);
-        // overlap_download: the caller's arrays already hold the factors
-        coarse_current = !in->host_current;
-        host_done = in->host_current;
-        sync_stats();
-        if (host_done) {
-            stats.t_d2h_ms = in->stats.t_d2h_ms;
-            stats.t_d2h_tail_ms = in->stats.t_d2h_tail_ms;
-            stats.d2h_bytes = in->stats.d2h_bytes;
-            stats.n_d2h_copies = in->stats.n_d2h_copies;
-        }
-    }
-    bool host_done = false;
-    void download() override {
-        in->sync();
-        if (host_done) return;
-        if (coarse_current) {
-            const auto t0 = std::chrono::steady_clock::now();
-            relayout(1);
-            t_compress = ms_since(t0);
-            coarse_current = false;
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        for (const Xfer &x : xfers()) HIPCHK(hipMemcpy(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost));
-        t_d2h = ms_since(t0);
-        sync_stats();
-    }
-    void snapshot() override { in->snapshot(); }
-    void restore() override {
-        in->restore();
-        coarse_current = true;
-        host_done = false;
-    }
-    void sync() override { in->sync(); }
-    void set_timing(int timing, int serial) override { in->set_timing(timing, serial); }
-    void solve(void *b, int64_t ldb, int nrhs) override {
-        in->solve(b, ldb, nrhs);
-        sync_stats();
-    }
-    void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) override {
-        in->set_a_pattern(ncol, xa, asub);
-        sync_stats();
-    }
-    void fill_a(const void *a, int on_device) override {
-        in->fill_a(a, on_device);
-        coarse_current = true;
-        host_done = false;
-        sync_stats();
-    }
-    void refine(const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) override {
-        in->refine(b, x, ld, nrhs, berr, steps);
-        sync_stats();
-    }
-    void check_exchange(int64_t *nsec, int64_t *nbytes) override { in->check_exchange(nsec, nbytes); }
-    ~AmalgPlan() override {
-        if (up_thread.joinable()) up_thread.join();
-        if (alloc_thread.joinable()) alloc_thread.join();
-        if (prog_thread.joinable()) prog_thread.join();
-        if (warm_thread.joinable()) warm_thread.join();
-    }
-};
-
-// ------------------------------------------------------------ grid amalgamation
-// The coarse partition on a Pr x Pc grid (csrc/amalg.h, "grids"): the
-// analysis runs on the ranks' supernode ranges, every fine block goes to
-// the owner of its coarse block (structure once, values at every upload and
-// back at download), and the inner Plan -- the ordinary grid plan -- runs on
-// each rank's local coarse LUstruct with the caller's communicator.  The
-// value relayout on the device: pack (k_amalg_l over the caller's L with a
-// row map, k_ranges over its U blocks) into one send buffer ordered by
-// destination, one section per ordered rank pair over the transport (RCCL
-// send / receive on the world communicator, or the host transports), unpack
-// (k_amalg_l / k_amalg_u) into the zeroed coarse storage; download runs the
-// same programs backwards.
-template <typename T, typename HT, typename LocalLU, typename LUS>
-struct GridAmalgPlan : PlanBase {
-    using Inner = Plan<T, HT, LocalLU, LUS>;
-    LUS *LU = nullptr;
-    int n = 0, ns = 0, Pr = 1, Pc = 1, iam = 0, P = 1;
-    slu_comm *comm = nullptr;
-    slu_engine_opts opts{};
-    bool dry = false;
-    GaFine f;
-    vector<const int_t *> flidx, fuidx;
-    GaChains ch;
-    GaPartition g;
-    GaRelay r;
-    vector<vector<i64>> cnt; // cnt[p][q]: values rank p sends rank q
-    // the coarse LUstruct the inner plan reads (index arrays only)
-    LUS mlu{};
-    LocalLU mllu{};
-    Glu_persist_t mglu{};
-    vector<int_t *> mlidx, muidx;
-    std::unique_ptr<Inner> in;
-    Xport X;
-    hipStream_t xs = nullptr; // plan-time exchanges before the inner plan exists
-    // device: caller layout, send / receive buffers, programs
-    DevBuf<T> d_oL, d_oU, d_send, d_recv;
-    DevBuf<LColX> d_pl, d_ul;
-    DevBuf<int32_t> d_plrow, d_ulrow, d_uucd;
-    DevBuf<uint16_t> d_uucl;
-    DevBuf<GaSpan> d_pu;
-    DevBuf<UChunk> d_uu;
-    DevBuf<i64> d_D;
-    double t_relay_plan = 0, t_expand = 0, t_compress = 0, t_h2d = 0, t_d2h = 0;
-    bool coarse_current = false;
-
-    static double ms_since(std::chrono::steady_clock::time_point t0) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-
-    // nullptr when nothing merges (every rank decides the same: the
-    // partition is all-gathered)
-    static GridAmalgPlan *make(LUS *lu, int n_, int pr, int pc, int iam_, slu_comm *c,
-                               const slu_engine_opts *o, double zero_frac, int maxw) {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::unique_ptr<GridAmalgPlan> G(new GridAmalgPlan);
-        G->LU = lu;
-        G->n = n_;
-        G->Pr = pr;
-        G->Pc = pc;
-        G->P = pr * pc;
-        G->iam = iam_;
-        G->comm = c;
-        if (o) G->opts = *o;
-        G->dry = G->opts.schedule_only != 0;
-        SLU_REQUIRE(c && (c->world || c->host_fn || c->host_p2p), "a %dx%d grid needs a communicator", pr, pc);
-        SLU_REQUIRE(G->P <= 32, "grid amalgamation: at most 32 ranks");
-        if (!G->dry) {
-            HIPCHK(hipSetDevice(c->device));
-            HIPCHK(hipStreamCreateWithFlags(&G->xs, hipStreamNonBlocking));
-        }
-        G->X.c = c;
-        G->X.s = G->xs;
-        G->X.host_mem = G->dry;
-        LocalLU *L = lu->Llu;
-        GaFine &f = G->f;
-        f.n = n_;
-        f.ns = G->ns = (int)(lu->Glu_persist->supno[n_ - 1] + 1);
-        f.Pr = pr;
-        f.Pc = pc;
-        f.myrow = iam_ / pc;
-        f.mycol = iam_ % pc;
-        f.xsup = lu->Glu_persist->xsup;
-        G->flidx.assign(L->Lrowind_bc_ptr, L->Lrowind_bc_ptr + f.nlc());
-        G->fuidx.assign(L->Ufstnz_br_ptr, L->Ufstnz_br_ptr + f.nlr());
-        f.lidx = G->flidx.data();
-        f.uidx = G->fuidx.data();
-        // 1. structure to the analysis owners, chains of my range
-        G->ch = ga_analyse(f, G->X.alltoallv(ga_structure_out(f)), zero_frac, maxw);
-        // 2. the partition
-        G->g = ga_partition(f, G->X.allgatherv(G_WORLD, G->ch.gstart));
-        if (G->g.ns2 == G->ns) return nullptr;
-        // 3. relayout: my pieces' structure to the coarse owners, my coarse
-        // LUstruct and programs from what arrives; everybody's counts
-        ga_send_side(f, G->g, G->r);
-        ga_receive_side(f, G->g, G->X.alltoallv(G->r.sstruct), G->r);
-        G->cnt = G->X.allgatherv(G_WORLD, G->r.scount);
-        for (int p = 0; p < G->P; ++p)
-            SLU_REQUIRE(G->cnt[p][iam_] == G->r.rcount[p], "grid amalgamation: counts %d -> %d", p, iam_);
-        G->t_relay_plan = ms_since(t0);
-        G->build_inner();
-        if (!G->dry) G->build_programs();
-        G->sync_stats();
-        G->stats.t_plan_ms = ms_since(t0);
-        return G.release();
-    }
-
-    void build_inner() {
-        mlidx.assign(r.nlc2, nullptr);
-        muidx.assign(r.nlr2, nullptr);
-        for (int j = 0; j < r.nlc2; ++j)
-            if (!r.Lidx2[j].empty()) mlidx[j] = r.Lidx2[j].data();
-        for (int j = 0; j < r.nlr2; ++j)
-            if (!r.Uidx2[j].empty()) muidx[j] = r.Uidx2[j].data();
-        mglu.xsup = g.xsup2.data();
-        mglu.supno = g.supno2.data();
-        mllu.Lrowind_bc_ptr = mlidx.data();
-        mllu.Ufstnz_br_ptr = muidx.data();
-        mlu.Glu_persist = &mglu;
-        mlu.Llu = &mllu;
-        slu_engine_opts io = opts;
-        io.overlap_upload = io.overlap_download = 0;
-        in.reset(new Inner(&mlu, n, Pr, Pc, iam, comm, &io));
-        if (!dry) X.s = in->stream; // the relayout's sections go on the kernels' stream
-    }
-
-    template <typename V> static void up(DevBuf<V> &d, const vector<V> &h) {
-        if (h.empty()) d.upload(vector<V>(1));
-        else d.upload(h);
-    }
-    void build_programs() {
-        up(d_pl, r.pack_l);
-        up(d_plrow, r.pack_lrow);
-        up(d_pu, r.pack_u);
-        up(d_ul, r.unpack_l);
-        up(d_ulrow, r.unpack_lrow);
-        up(d_uu, r.unpack_u);
-        up(d_uucd, r.unpack_ucd);
-        up(d_uucl, r.unpack_ucl);
-        up(d_D, r.D);
-        d_send.alloc(std::max<i64>(r.soff[P], 1));
-        d_recv.alloc(std::max<i64>(r.received, 1));
-    }
-    void ensure_o() {
-        if (d_oL.p) return;
-        d_oL.alloc(std::max<i64>(r.lval, 1));
-        d_oU.alloc(std::max<i64>(r.uval, 1));
-    }
-    // the caller's local values <-> d_oL / d_oU
-    vector<Xfer> xfers() {
-        ensure_o();
-        LocalLU *L = LU->Llu;
-        vector<Xfer> v;
-        for (int j = 0; j < f.nlc(); ++j)
-            if (L->Lrowind_bc_ptr[j] && r.lsrc[j + 1] > r.lsrc[j])
-                v.push_back({(char *)(d_oL.p + r.lsrc[j]), (char *)L->Lnzval_bc_ptr[j],
-                             (size_t)(r.lsrc[j + 1] - r.lsrc[j]) * sizeof(T)});
-        for (int j = 0; j < f.nlr(); ++j)
-            if (L->Ufstnz_br_ptr[j] && r.usrc[j + 1] > r.usrc[j])
-                v.push_back({(char *)(d_oU.p + r.usrc[j]), (char *)L->Unzval_br_ptr[j],
-                             (size_t)(r.usrc[j + 1] - r.usrc[j]) * sizeof(T)});
-        return merge_xfers(std::move(v));
-    }
-
-    void launch_l(const DevBuf<LColX> &items, size_t nitems, const DevBuf<int32_t> &lrow, T *o, T *m, int dir,
-                  hipStream_t st) {
-        if (nitems)
-            hipLaunchKernelGGL((k_amalg_l<T>), dim3((unsigned)nitems), dim3(256), 0, st, items.p, lrow.p, o, m, dir);
-    }
-    // the value all-to-all: forward p -> q from send to receive regions,
-    // backward q -> p the other way; my own pair is a device copy
-    void exchange(bool forward) {
-        hipStream_t st = in->stream;
-        const int me = iam;
-        if (r.scount[me])
-            HIPCHK(hipMemcpyAsync(forward ? d_recv.p + r.roff[me] : d_send.p + r.soff[me],
-                                  forward ? d_send.p + r.soff[me] : d_recv.p + r.roff[me],
-                                  (size_t)r.scount[me] * sizeof(T), hipMemcpyDeviceToDevice, st));
-        for (int p = 0; p < P; ++p)
-            for (int q = 0; q < P; ++q) {
-                if (p == q || !cnt[p][q]) continue;
-                const int root = forward ? p : q, dest = forward ? q : p;
-                T *buf = nullptr;
-                if (me == p) buf = d_send.p + r.soff[q];
-                else if (me == q) buf = d_recv.p + r.roff[p];
-                X.section(G_WORLD, root, 1u << dest, buf, (size_t)cnt[p][q] * sizeof(T));
-            }
-        X.phase = forward ? "grid amalgamation relayout (values to the coarse owners)"
-                          : "grid amalgamation relayout (factors back to the caller layout)";
-        X.flush();
-        X.phase = "plan-time exchange";
-    }
-
-    void expand() { // caller layout (d_oL / d_oU) -> coarse
-        const auto t0 = std::chrono::steady_clock::now();
-        hipStream_t st = in->stream;
-        launch_l(d_pl, r.pack_l.size(), d_plrow, d_send.p, d_oL.p, 1, st);
-        if (!r.pack_u.empty())
-            hipLaunchKernelGGL((k_ranges<T>), dim3((unsigned)((r.pack_u.size() + 255) / 256)), dim3(256), 0, st,
-                               d_pu.p, (int)r.pack_u.size(), d_oU.p, d_send.p, 0);
-        HIPCHK(hipGetLastError());
-        exchange(true);
-        HIPCHK(hipMemsetAsync(in->d_L.p, 0, in->d_L.bytes(), st));
-        HIPCHK(hipMemsetAsync(in->d_U.p, 0, in->d_U.bytes(), st));
-        launch_l(d_ul, r.unpack_l.size(), d_ulrow, d_recv.p, in->d_L.p, 0, st);
-        if (!r.unpack_u.empty())
-            hipLaunchKernelGGL((k_amalg_u<T>), dim3((unsigned)((r.unpack_u.size() + 3) / 4)), dim3(256), 0, st,
-                               d_uu.p, (int)r.unpack_u.size(), d_uucd.p, d_uucl.p, d_D.p, (i64)r.DL0, d_recv.p, in->d_L.p,
-                               in->d_U.p, 0);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-        t_expand = ms_since(t0);
-    }
-    void compress() { // coarse -> caller layout
-        const auto t0 = std::chrono::steady_clock::now();
-        hipStream_t st = in->stream;
-        launch_l(d_ul, r.unpack_l.size(), d_ulrow, d_recv.p, in->d_L.p, 1, st);
-        if (!r.unpack_u.empty())
-            hipLaunchKernelGGL((k_amalg_u<T>), dim3((unsigned)((r.unpack_u.size() + 3) / 4)), dim3(256), 0, st,
-                               d_uu.p, (int)r.unpack_u.size(), d_uucd.p, d_uucl.p, d_D.p, (i64)r.DL0, d_recv.p, in->d_L.p,
-                               in->d_U.p, 1);
-        HIPCHK(hipGetLastError());
-        exchange(false);
-        launch_l(d_pl, r.pack_l.size(), d_plrow, d_send.p, d_oL.p, 0, st);
-        if (!r.pack_u.empty())
-            hipLaunchKernelGGL((k_ranges<T>), dim3((unsigned)((r.pack_u.size() + 255) / 256)), dim3(256), 0, st,
-                               d_pu.p, (int)r.pack_u.size(), d_oU.p, d_send.p, 1);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-        t_compress = ms_since(t0);
-    }
-
-    void sync_stats() {
-        stats = in->stats;
-        std::copy(in->path_counts, in->path_counts + PlanBase::PC_N, this->path_counts);
-        const bool cp = sizeof(T) == 16;
-        const AmalgFlops &F = ch.fl; // my analysis range's share of the caller partition's work
-        stats.schur_flops = F.schur * (cp ? 4.0 : 1.0);
-        stats.panel_flops = (cp ? 6 * F.s1 + 10 * F.w + 8 * F.s2 : F.s1 + 2 * F.s2) +
-                            (cp ? 4.0 : 1.0) * F.trsm + F.trsv;
-        stats.nsupers_in = ns;
-        i64 groups = 0;
-        for (size_t i = 0; i < ch.gstart.size(); ++i) {
-            const i64 e = i + 1 < ch.gstart.size() ? ch.gstart[i + 1]
-                                                   : (i64)ga_range(ns, P, iam + 1);
-            groups += e - ch.gstart[i] > 1;
-        }
-        stats.amalg_groups = groups;
-        stats.t_amalg_ms = t_relay_plan;
-        stats.t_expand_ms = t_expand;
-        stats.t_compress_ms = t_compress;
-        stats.t_upload_ms = t_h2d;
-        stats.t_d2h_ms = t_d2h;
-        stats.h2d_bytes = (double)(r.lval + r.uval) * sizeof(T);
-        stats.d2h_bytes = stats.h2d_bytes;
-    }
-
-    void upload() override {
-        const auto t0 = std::chrono::steady_clock::now();
-        staged_h2d(xfers(), comm->device);
-        t_h2d = ms_since(t0);
-        expand();
-        in->vstate = 1;
-        in->d_acur = nullptr;
-        in->host_current = false;
-        coarse_current = false;
-        sync_stats();
-    }
-    void adopt_factors() override {
-        upload();
-        in->sync();
-        in->vstate = 2;
-    }
-    void factor(double anorm, int *info, int *tiny) override {
-        in->factor(anorm, info, tiny);
-        coarse_current = true;
-        sync_stats();
-    }
-    void download() override {
-        in->sync();
-        if (coarse_current) {
-            ensure_o();
-            compress();
-            coarse_current = false;
-        }
-        const auto t0 = std::chrono::steady_clock::now();
-        for (const Xfer &x : xfers()) HIPCHK(hipMemcpy(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost));
-        t_d2h = ms_since(t0);
-        sync_stats();
-    }
-    void snapshot() override { in->snapshot(); }
-    void restore() override {
-        in->restore();
-        coarse_current = true;
-    }
-    void sync() override { in->sync(); }
-    void set_timing(int timing, int serial) override { in->set_timing(timing, serial); }
-    void solve(void *b, int64_t ldb, int nrhs) override {
-        in->solve(b, ldb, nrhs);
-        sync_stats();
-    }
-    void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) override {
-        in->set_a_pattern(ncol, xa, asub);
-        sync_stats();
-    }
-    void fill_a(const void *a, int on_device) override {
-        in->fill_a(a, on_device);
-        coarse_current = true;
-        sync_stats();
-    }
-    void refine(const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) override {
-        in->refine(b, x, ld, nrhs, berr, steps);
-        sync_stats();
-    }
-    void check_exchange(int64_t *nsec, int64_t *nbytes) override {
-        in->check_exchange(nsec, nbytes);
-        sync_stats();
-    }
-    ~GridAmalgPlan() override {
-        in.reset();
-        if (xs) (void)hipStreamDestroy(xs);
-    }
-};
-
-// The plan for a caller's LUstruct: the amalgamated one when chains merge
-// (1x1: AmalgPlan; 2D grids: GridAmalgPlan; SLU_AMALG=0 turns it off;
-// SLU_AMALG_ZERO sets the explicit zero fraction, default 0.10), else the
-// plain plan.  3D grids factor the caller's partition (its forests).
-template <typename P> PlanBase *make_plan_any(void *LU, int n, int pr, int pc, int iam, slu_comm *c,
-                                              const slu_engine_opts *o) {
-    using A = AmalgPlan<typename P::value_type, typename P::host_type, typename P::local_type,
-                        typename P::lus_type>;
-    using GA = GridAmalgPlan<typename P::value_type, typename P::host_type, typename P::local_type,
-                             typename P::lus_type>;
-    const char *e = getenv("SLU_AMALG");
-    const bool on = !(e && !strcmp(e, "0"));
-    const char *z = getenv("SLU_AMALG_ZERO");
-    const double zf = z ? atof(z) : 0.10;
-    if (on && pr * pc == 1 && !(o && o->schedule_only) && !(c && c->npdep > 1)) {
-        if (PlanBase *p = A::make((typename P::lus_type *)LU, n, o, zf, FAST_MAXW)) return p;
-    } else if (on && pr * pc > 1 && !(c && c->npdep > 1)) {
-        if (PlanBase *p = GA::make((typename P::lus_type *)LU, n, pr, pc, iam, c, o, zf, FAST_MAXW)) return p;
-    }
-    return make_plan<P>(LU, n, pr, pc, iam, c, o);
-}
-
 } // namespace slu
+
+#include "plan_amalg.h" // the amalgamated plans over Plan, make_plan_any
 
 struct slu_plan {
     int dtype = 0;
@@ -5206,10 +3773,39 @@ __global__ void __launch_bounds__(1024) k_poison_lds(double v, int bytes) {
         s_poison[0] = 0; // never true; keeps the stores
 }
 
+// No exception leaves the C ABI: runs fn and returns 0 (or fn's pointer); on
+// an exception stores its text for slu_last_error() and returns -1 (nullptr).
+template <typename F> static auto guarded(F &&fn) {
+    using R = decltype(fn());
+    try {
+        if constexpr (std::is_void<R>::value) {
+            fn();
+            return 0;
+        } else {
+            return fn();
+        }
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        if constexpr (std::is_void<R>::value) return -1;
+        else return R(nullptr);
+    }
+}
+
+static slu_comm *new_comm(int nprow, int npcol, int iam, int device) {
+    auto *c = new slu_comm;
+    c->nprow = nprow;
+    c->npcol = npcol;
+    c->iam = iam;
+    c->myrow = iam / npcol;
+    c->mycol = iam % npcol;
+    c->device = device;
+    return c;
+}
+
 extern "C" {
 
 int slu_debug_poison_lds(int device) {
-    try {
+    return guarded([&] {
         HIPCHK(hipSetDevice(device));
         // the whole 160 KB per workgroup where the runtime allows it, else 64 KB
         int bytes = 160 * 1024;
@@ -5221,36 +3817,22 @@ int slu_debug_poison_lds(int device) {
         hipLaunchKernelGGL(k_poison_lds, dim3(4096), dim3(1024), bytes, 0, __builtin_nan(""), bytes);
         HIPCHK(hipGetLastError());
         HIPCHK(hipDeviceSynchronize());
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 const char *slu_last_error(void) { return g_last_error.c_str(); }
 
 int slu_comm_unique_id(void *uid) {
-    try {
+    return guarded([&] {
         ncclUniqueId id;
         NCCLCHK(ncclGetUniqueId(&id));
         memcpy(uid, &id, sizeof id);
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 slu_comm *slu_comm_create(const void *uid, int nprow, int npcol, int iam, int device) {
-    try {
-        auto *c = new slu_comm;
-        c->nprow = nprow;
-        c->npcol = npcol;
-        c->iam = iam;
-        c->myrow = iam / npcol;
-        c->mycol = iam % npcol;
-        c->device = device;
+    return guarded([&]() -> slu_comm * {
+        slu_comm *c = new_comm(nprow, npcol, iam, device);
         HIPCHK(hipSetDevice(device));
         if (nprow * npcol > 1) {
             SLU_REQUIRE(uid != nullptr, "uid required for a %dx%d grid", nprow, npcol);
@@ -5261,28 +3843,19 @@ slu_comm *slu_comm_create(const void *uid, int nprow, int npcol, int iam, int de
             NCCLCHK(ncclCommSplit(c->world, c->mycol, c->myrow, &c->col, nullptr));
         }
         return c;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return nullptr;
-    }
+    });
 }
 
 slu_comm *slu_comm_create3d(const void *uid, int nprow, int npcol, int npdep, int iam3d, int device) {
-    try {
+    return guarded([&]() -> slu_comm * {
         const int P = nprow * npcol;
         SLU_REQUIRE(nprow > 0 && npcol > 0 && npdep > 0 && (npdep & (npdep - 1)) == 0,
                     "3D grid %dx%dx%d: Pz must be a power of two", nprow, npcol, npdep);
         SLU_REQUIRE(iam3d >= 0 && iam3d < P * npdep, "rank %d outside a %dx%dx%d grid", iam3d, nprow,
                     npcol, npdep);
-        auto *c = new slu_comm;
-        c->nprow = nprow;
-        c->npcol = npcol;
+        slu_comm *c = new_comm(nprow, npcol, iam3d % P, device);
         c->npdep = npdep;
         c->zlayer = iam3d / P;
-        c->iam = iam3d % P;
-        c->myrow = c->iam / npcol;
-        c->mycol = c->iam % npcol;
-        c->device = device;
         HIPCHK(hipSetDevice(device));
         if (P * npdep > 1) {
             SLU_REQUIRE(uid != nullptr, "uid required for a %dx%dx%d grid", nprow, npcol, npdep);
@@ -5295,67 +3868,43 @@ slu_comm *slu_comm_create3d(const void *uid, int nprow, int npcol, int npdep, in
             NCCLCHK(ncclCommSplit(c->world, c->mycol, c->myrow, &c->col, nullptr));
         }
         return c;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return nullptr;
-    }
+    });
 }
 
 slu_comm *slu_comm_create_host_p2p3d(slu_host_p2p_fn fn, void *ctx, int nprow, int npcol, int npdep,
                                      int iam3d, int device) {
-    try {
+    return guarded([&]() -> slu_comm * {
         SLU_REQUIRE(npdep > 0 && (npdep & (npdep - 1)) == 0, "Pz = %d is not a power of two", npdep);
         slu_comm *c = slu_comm_create_host_p2p(fn, ctx, nprow, npcol, iam3d % (nprow * npcol), device);
         if (!c) return nullptr;
         c->npdep = npdep;
         c->zlayer = iam3d / (nprow * npcol);
         return c;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return nullptr;
-    }
+    });
 }
 
 slu_comm *slu_comm_create_host(slu_host_bcast_fn fn, void *ctx, int nprow, int npcol, int iam,
                                int device) {
-    try {
+    return guarded([&]() -> slu_comm * {
         SLU_REQUIRE(fn != nullptr, "host transport needs a broadcast callback");
-        auto *c = new slu_comm;
-        c->nprow = nprow;
-        c->npcol = npcol;
-        c->iam = iam;
-        c->myrow = iam / npcol;
-        c->mycol = iam % npcol;
-        c->device = device;
+        slu_comm *c = new_comm(nprow, npcol, iam, device);
         c->host_fn = fn;
         c->host_ctx = ctx;
         HIPCHK(hipSetDevice(device));
         return c;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return nullptr;
-    }
+    });
 }
 
 slu_comm *slu_comm_create_host_p2p(slu_host_p2p_fn fn, void *ctx, int nprow, int npcol, int iam,
                                    int device) {
-    try {
+    return guarded([&]() -> slu_comm * {
         SLU_REQUIRE(fn != nullptr, "point-to-point host transport needs a callback");
-        auto *c = new slu_comm;
-        c->nprow = nprow;
-        c->npcol = npcol;
-        c->iam = iam;
-        c->myrow = iam / npcol;
-        c->mycol = iam % npcol;
-        c->device = device;
+        slu_comm *c = new_comm(nprow, npcol, iam, device);
         c->host_p2p = fn;
         c->host_ctx = ctx;
         if (device >= 0) HIPCHK(hipSetDevice(device)); // -1: schedule-only plans, no GPU
         return c;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return nullptr;
-    }
+    });
 }
 
 int slu_comm_size(const slu_comm *c, int group) {
@@ -5408,147 +3957,91 @@ slu_plan *slu_plan_create(int dtype, void *LU, int n, int nprow, int npcol, int 
 }
 
 int slu_plan_gather3d(slu_plan *p) {
-    try {
+    return guarded([&] {
         p->impl->gather_layers();
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_adopt_factors(slu_plan *p) {
-    try {
+    return guarded([&] {
         p->impl->adopt_factors();
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_upload(slu_plan *p) {
-    try {
+    return guarded([&] {
         p->impl->upload();
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_factor(slu_plan *p, double anorm, int *info, int *tiny) {
-    try {
+    return guarded([&] {
         int i = 0, t = 0;
         p->impl->factor(anorm, &i, &t);
         if (info) *info = i;
         if (tiny) *tiny = t;
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_solve(slu_plan *p, void *b, int64_t ldb, int nrhs) {
-    try {
+    return guarded([&] {
         p->impl->solve(b, ldb, nrhs);
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_set_a_pattern(slu_plan *p, int64_t ncol, const int64_t *xa, const int64_t *asub) {
-    try {
+    return guarded([&] {
         p->impl->set_a_pattern(ncol, xa, asub);
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_fill_a(slu_plan *p, const void *a, int on_device) {
-    try {
+    return guarded([&] {
         p->impl->fill_a(a, on_device);
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_refine(slu_plan *p, const void *b, void *x, int64_t ld, int nrhs, double *berr,
                     int *steps) {
-    try {
+    return guarded([&] {
         p->impl->refine(b, x, ld, nrhs, berr, steps);
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_download(slu_plan *p) {
-    try {
+    return guarded([&] {
         p->impl->download();
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_snapshot(slu_plan *p) {
-    try {
+    return guarded([&] {
         p->impl->snapshot();
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_restore(slu_plan *p) {
-    try {
+    return guarded([&] {
         p->impl->restore();
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_check_exchange(slu_plan *p, int64_t *nsections, int64_t *nbytes) {
-    try {
+    return guarded([&] {
         p->impl->check_exchange(nsections, nbytes);
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_set_timing(slu_plan *p, int timing, int serial) {
-    try {
+    return guarded([&] {
         p->impl->set_timing(timing, serial);
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 int slu_plan_sync(slu_plan *p) {
-    try {
+    return guarded([&] {
         p->impl->sync();
-        return 0;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        return -1;
-    }
+    });
 }
 
 void slu_plan_destroy(slu_plan *p) { delete p; }

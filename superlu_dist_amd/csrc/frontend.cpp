@@ -370,8 +370,8 @@ static void coarsen(slu_symb *S) {
     A.programs = false; // the structure is all the coarse symbolic needs
     const bool merged = A.build(S->n, ns, S->xsup.data(), li.data(), ui.data(), 0.10, 256);
     slu_lustruct_free(LU, SLU_D);
-    S->fl[0] = A.fl_schur; S->fl[1] = A.fl_trsm; S->fl[2] = A.fl_trsv;
-    S->fl[3] = A.fl_s1; S->fl[4] = A.fl_s2; S->fl[5] = A.fl_w;
+    S->fl[0] = A.fl.schur; S->fl[1] = A.fl.trsm; S->fl[2] = A.fl.trsv;
+    S->fl[3] = A.fl.s1; S->fl[4] = A.fl.s2; S->fl[5] = A.fl.w;
     if (!merged) return;
     A.coarse_glu(S->xlsub, S->lsub, S->xusub, S->usub);
     S->nsupers = A.ns2;

@@ -130,12 +130,15 @@ def test_gpu_factors_finite_with_poisoned_lds(kind, dims, dtype):
     assert err < TOL[dtype], err
 
 
-@pytest.mark.parametrize("slot_kb,dtype,d2h_mode", [
-    pytest.param(64, 0, None, id="64-0"), pytest.param(1024, 1, None, id="1024-1"),
-    pytest.param(256, 2, None, id="256-2"), pytest.param(0, 0, None, id="0-0"),
-    pytest.param(64, 0, "push", id="64-0-push"),   # SLU_D2H_MODE=push: zero-copy into the pinned slots
+@pytest.mark.parametrize("slot_kb,dtype,d2h_mode,reference", [
+    pytest.param(64, 0, None, False, id="64-0"), pytest.param(1024, 1, None, False, id="1024-1"),
+    pytest.param(256, 2, None, False, id="256-2"), pytest.param(0, 0, None, False, id="0-0"),
+    pytest.param(64, 0, "push", False, id="64-0-push"),   # SLU_D2H_MODE=push: zero-copy into the pinned slots
+    # the reference's own (fine) structure: the amalgamated plan, whose fills
+    # carry the caller's layout and compress each level before it is pushed
+    pytest.param(64, 0, None, True, id="64-0-reference"),
 ])
-def test_gpu_overlapped_upload_download(slot_kb, dtype, d2h_mode, monkeypatch):
+def test_gpu_overlapped_upload_download(slot_kb, dtype, d2h_mode, reference, monkeypatch):
     """The drop-in path's copies (hostio.h): the values go up beside the plan
     build, each level's factors come back while later levels run, through
     pinned slots (tiny slots here, so blocks split across fills)."""
@@ -145,7 +148,7 @@ def test_gpu_overlapped_upload_download(slot_kb, dtype, d2h_mode, monkeypatch):
         monkeypatch.setenv("SLU_D2H_MODE", d2h_mode)
     kw = dict(diag=6 - 0.25, diag_im=-0.0025) if dtype == 2 else {}
     A = Csc.stencil(STENCIL_3D7, 14, 14, 14, dtype=dtype, **kw)
-    S = Symbolic(A, nd_order(14, 14, 14), 60, 256)
+    S = Symbolic(A, nd_order(14, 14, 14), 60, 256, reference=reference)
     gpu, ref = S.distribute(), S.distribute()
     an = cases.anorm(A)
     p = Plan(gpu, overlap_upload=True, overlap_download=True)
@@ -155,6 +158,8 @@ def test_gpu_overlapped_upload_download(slot_kb, dtype, d2h_mode, monkeypatch):
     assert p.factor(an) == (0, 0)
     p.download()                           # a no-op: already written back
     st = p.stats()
+    if reference:
+        assert st["nsupers"] < st["nsupers_in"]   # the amalgamated plan ran
     vb = (gpu.Lval.size - 1 + gpu.Uval.size - 1) * gpu.Lval.itemsize  # the caller's values
     assert st["d2h_bytes"] == vb and st["h2d_bytes"] == vb
     pyoracle.oracle_factor([ref], 1, 1, A.n, False, an)
