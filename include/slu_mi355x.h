@@ -247,6 +247,25 @@ int slu_plan_fill_a(slu_plan *p, const void *a, int on_device);
  * (stat->RefineSteps).  t_refine_ms in the stats = device time of the call. */
 int slu_plan_refine(slu_plan *p, const void *b, void *x, int64_t ld, int nrhs, double *berr,
                     int *steps);
+/* Mixed precision, real fp32 plans (SLU_S) only: the factors in fp32, the
+ * caller's A, b and x in fp64 (the scheme of psgsrfs_d2, SRC/psgsrfs_d2.c).
+ * fill_a_d2: slu_plan_fill_a from nnz fp64 values; L and U receive
+ * (float)a[e], round to nearest even, in the one pass that reads the doubles,
+ * and the fp64 values stay on the device for the residual (on_device = 0: in
+ * a buffer of the plan; on_device = 1: the caller's device pointer, which
+ * must stay valid).  The plain slu_plan_refine refuses factors of such a
+ * fill: no fp32 A exists.
+ * refine_d2: the loop of slu_plan_refine with fp64's eps / safmin, on the A
+ * of the slu_plan_fill_a_d2 the factors came from.  Per column: r = b - A x,
+ * berr and rmax = max_i |r_i| in fp64; while continuing, with rmax = m 2^e,
+ * m in [0.5, 1) (e = 0 if rmax is 0 or not finite): dx = the fp32 solve of
+ * (float)(r 2^-e), x += 2^e dx in fp64.  b, x: host fp64 arrays (ld ld);
+ * x in = initial iterate (zeros allowed: the first step is then the plain
+ * solve), out = refined.  berr, steps, t_refine_ms, 2D grids (collective)
+ * and 3D plans (refused) as for slu_plan_refine. */
+int slu_plan_fill_a_d2(slu_plan *p, const double *a, int on_device);
+int slu_plan_refine_d2(slu_plan *p, const double *b, double *x, int64_t ld, int nrhs,
+                       double *berr, int *steps);
 /* Schedule-only plans: replay every level's exchange phases of
  * slu_plan_factor through the communicator on host buffers; each received
  * section is checked byte for byte against what its root wrote.  Collective;

@@ -48,6 +48,7 @@
 #include "diag_wave.h"
 #include "fill.h"
 #include "solve.h"
+#include "refine_d2.h"
 #include "hostio.h"
 #include "amalg.h"
 #include "amalg_dev.h"
@@ -294,6 +295,9 @@ struct PlanBase {
     virtual void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) = 0;
     virtual void fill_a(const void *a, int on_device) = 0;
     virtual void refine(const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) = 0;
+    // fp32 plans: fp64 values of A, fp64 residual and update (refine_d2.h)
+    virtual void fill_a_d2(const double *a, int on_device) = 0;
+    virtual void refine_d2(const double *b, double *x, int64_t ld, int nrhs, double *berr, int *steps) = 0;
     virtual void check_exchange(int64_t *nsec, int64_t *nbytes) = 0;
     virtual void gather_layers() { throw Error("gather_layers: not a 3D plan"); }
     virtual void adopt_factors() = 0; // upload host values that are already factors
@@ -2369,8 +2373,11 @@ struct Plan : PlanBase {
     // of A not yet factored (upload / restore / fill_a), 2 factors of them.
     // d_acur = the values of A behind the storage (fill_a only; an upload
     // does not tell which A it came from), a_fact = d_acur of the factors.
+    // d_acur64 / a_fact64 / snap_acur64: the same for the fp64 values an
+    // fp32 plan got through fill_a_d2 (then d_acur is null: no fp32 A exists).
     int vstate = 0;
     const T *a_fact = nullptr, *snap_acur = nullptr;
+    const double *d_acur64 = nullptr, *a_fact64 = nullptr, *snap_acur64 = nullptr;
     int snap_state = 0;
 
     // ---- host <-> HBM copies of the values (hostio.h)
@@ -2419,6 +2426,7 @@ struct Plan : PlanBase {
         stats.t_upload_ms = up_ms;
         vstate = 1;
         d_acur = nullptr;
+        d_acur64 = nullptr;
         host_current = true;
     }
 
@@ -2580,11 +2588,13 @@ struct Plan : PlanBase {
         HIPCHK(hipStreamSynchronize(stream));
         snap_state = vstate;
         snap_acur = d_acur;
+        snap_acur64 = d_acur64;
     }
     void restore() override {
         SLU_REQUIRE(d_L0.p && d_U0.p, "restore without snapshot");
         vstate = snap_state;
         d_acur = snap_acur;
+        d_acur64 = snap_acur64;
         host_current = false;
         HIPCHK(hipMemcpyAsync(d_L.p, d_L0.p, d_L.bytes(), hipMemcpyDeviceToDevice, stream));
         HIPCHK(hipMemcpyAsync(d_U.p, d_U0.p, d_U.bytes(), hipMemcpyDeviceToDevice, stream));
@@ -2597,6 +2607,8 @@ struct Plan : PlanBase {
         upload();
         sync();
         vstate = 2;
+        a_fact = nullptr; // adopted factors: of no A this plan knows
+        a_fact64 = nullptr;
     }
     void sync() override {
         HIPCHK(hipStreamSynchronize(pstream));
@@ -2965,6 +2977,7 @@ struct Plan : PlanBase {
                                 : "upload or fill_a first");
         vstate = 2;
         a_fact = d_acur;
+        a_fact64 = d_acur64;
         // thresh = smach_dist("Epsilon") * anorm (SRC/pdgstrf.c:412-413); in
         // psgstrf thresh is a float product.
         const float s_eps = 5.9604644775390625e-08f; // FLT_EPSILON * 0.5
@@ -3565,6 +3578,120 @@ struct Plan : PlanBase {
         stats.t_refine_ms = ms;
     }
 
+    // Mixed-precision refinement of an fp32 plan (refine_d2.h): the loop of
+    // refine() with fp64's constants on the fp64 A of fill_a_d2; b, x, the
+    // residual and the update in fp64, the correction from the fp32 sweep of
+    // the residual scaled by 2^-e, rmax = m 2^e with m in [0.5, 1).
+    DevBuf<double> d_d2_b, d_d2_x, d_d2_r, d_d2_sr;
+    DevBuf<unsigned long long> d_d2_max; // bit patterns of berr, rmax
+
+    // berr and rmax of the current x: mx[0], mx[1]
+    void resid_d2(double safe1, double safe2, double mx[2]) {
+        const unsigned rb = (unsigned)((n + 255) / 256);
+        unsigned long long bits[2] = {0, 0};
+        HIPCHK(hipMemsetAsync(d_d2_max.p, 0, sizeof bits, stream));
+        if (!xmode) {
+            hipLaunchKernelGGL(k_resid_d2, dim3(rb), dim3(256), 0, stream, d_rp.p, d_rc.p, d_re.p, a_fact64,
+                               d_d2_x.p, d_d2_b.p, d_d2_r.p, n, safe1, safe2, d_d2_max.p);
+        } else {
+            X.s = stream;
+            hipLaunchKernelGGL(k_resid_part_d2, dim3(rb), dim3(256), 0, stream, d_rp.p, d_rc.p, d_re.p,
+                               a_fact64, d_d2_x.p, d_d2_r.p, d_rf_s.p, n);
+            for (const auto &q : rf_secs) { // the sections of resid_2d, r_p as doubles
+                const int k = (int)q[0], c = (int)q[1], oc = k % Pc;
+                const size_t w = (size_t)W(k);
+                void *br = mycol == c ? (void *)(d_d2_r.p + xsup[k]) : mycol == oc ? (void *)(d_d2_sr.p + q[2]) : nullptr;
+                void *bs = mycol == c ? (void *)(d_rf_s.p + xsup[k]) : mycol == oc ? (void *)(d_rf_ss.p + q[2]) : nullptr;
+                X.section(G_ROW, c, 1u << oc, br, w * sizeof(double));
+                X.section(G_ROW, c, 1u << oc, bs, w * sizeof(double));
+            }
+            X.flush();
+            if (!rf_rows_h.empty())
+                hipLaunchKernelGGL(k_resid_fin_d2, dim3((unsigned)rf_rows_h.size()), dim3(256), 0, stream,
+                                   d_rf_rows.p, d_d2_b.p, d_d2_r.p, d_rf_s.p, d_d2_sr.p, d_rf_ss.p, safe1,
+                                   safe2, d_d2_max.p);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(bits, d_d2_max.p, sizeof bits, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (xmode) { // the maxima over the diagonal owners (NaN above +Inf as a bit pattern)
+            auto all = X.allgatherv(G_WORLD, vector<i64>{(i64)bits[0], (i64)bits[1]});
+            bits[0] = bits[1] = 0;
+            for (auto &v : all)
+                for (int t = 0; t < 2; ++t) bits[t] = std::max(bits[t], (unsigned long long)v[t]);
+        }
+        memcpy(mx, bits, sizeof bits);
+    }
+
+    void refine_d2(const double *b, double *x, int64_t ld, int nrhs, double *berr, int *steps) override {
+        if constexpr (std::is_same<T, float>::value) {
+            SLU_REQUIRE(!zmode, "refine_d2: not on 3D plans");
+            SLU_REQUIRE(vstate == 2, "refine_d2: the device storage holds no factors (factor first)");
+            SLU_REQUIRE(a_fact64 != nullptr,
+                        "refine_d2 needs the fp64 values of A the factors came from "
+                        "(slu_plan_fill_a_d2 before slu_plan_factor)");
+            SLU_REQUIRE(ld >= n && nrhs >= 0, "refine_d2: ld %lld < n %d", (long long)ld, n);
+            if (!sv_ready) build_solve();
+            const double eps = 0.5 * 2.220446049250313e-16, safmin = 2.2250738585072014e-308;
+            const double safe1 = (double)(n + 1) * safmin, safe2 = safe1 / eps;
+            const size_t nn = (size_t)std::max(n, 1);
+            if (d_d2_b.n != nn) {
+                d_d2_b.alloc(nn);
+                d_d2_x.alloc(nn);
+                d_d2_r.alloc(nn);
+                d_d2_max.alloc(2);
+            }
+            if (d_rf_r.n != nn) d_rf_r.alloc(nn); // the fp32 residual / correction
+            if (xmode) {
+                if (rf_rows_h.empty() && rf_secs.empty()) build_refine_2d();
+                if (d_d2_sr.n != d_rf_sr.n) d_d2_sr.alloc(d_rf_sr.n);
+            }
+            const unsigned rb = (unsigned)((n + 255) / 256);
+            hipEvent_t e0, e1;
+            HIPCHK(hipEventCreate(&e0));
+            HIPCHK(hipEventCreate(&e1));
+            HIPCHK(hipStreamSynchronize(pstream));
+            HIPCHK(hipEventRecord(e0, stream));
+            for (int j = 0; j < nrhs; ++j) {
+                double *hx = x + (i64)j * ld;
+                HIPCHK(hipMemcpyAsync(d_d2_b.p, b + (i64)j * ld, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
+                HIPCHK(hipMemcpyAsync(d_d2_x.p, hx, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
+                int count = 0;
+                double lstres = 3.0, mx[2] = {0.0, 0.0};
+                while (true) {
+                    resid_d2(safe1, safe2, mx);
+                    const double be = mx[0], rmax = mx[1];
+                    if (!(be > eps && be * 2 <= lstres && count < 20)) break;
+                    int e = 0;
+                    if (rmax > 0.0 && std::isfinite(rmax)) (void)frexp(rmax, &e);
+                    hipLaunchKernelGGL(k_scale_cvt_d2, dim3(rb), dim3(256), 0, stream, d_d2_r.p, d_rf_r.p, n, e);
+                    if (xmode) {
+                        sv_gather(d_rf_r.p); // the owners' rows of r32 to every rank, then the 2D solve
+                        sweep_2d(d_rf_r.p);
+                    } else {
+                        sweep(d_rf_r.p);
+                    }
+                    hipLaunchKernelGGL(k_axpy_d2, dim3(rb), dim3(256), 0, stream, d_d2_x.p, d_rf_r.p, n, e);
+                    lstres = be;
+                    ++count;
+                }
+                HIPCHK(hipMemcpyAsync(hx, d_d2_x.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                if (berr) berr[j] = mx[0];
+                if (steps) steps[j] = count;
+            }
+            HIPCHK(hipEventRecord(e1, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+            stats.t_refine_ms = ms;
+        } else {
+            throw Error(fmt("refine_d2: fp32 plans only, this plan's dtype is %s", dtype_name()));
+        }
+    }
+
     // ------------------------------------------------------- values of A
     // SamePattern_SameRowPerm refill (SRC/pddistribute.c:545-672) on the
     // device: the destination of every nonzero of A in this rank's L/U
@@ -3575,6 +3702,7 @@ struct Plan : PlanBase {
     // skipped (:587,596).
     DevBuf<i64> d_amap;
     DevBuf<T> d_aval;
+    DevBuf<double> d_aval64; // fill_a_d2's host values (allocated at first use)
     i64 a_nnz = -1;
 
     bool has_block(int gb, int jb) const { // this rank holds L(gb,jb) (gb >= jb) or U(gb,jb)
@@ -3641,6 +3769,7 @@ struct Plan : PlanBase {
         atick("map upload");
         a_nnz = nnz;
         d_acur = a_fact = snap_acur = nullptr; // the previous pattern's values are gone
+        d_acur64 = a_fact64 = snap_acur64 = nullptr;
         {   // rows of A for the refinement's residual (k_resid): all of A on a
             // 1x1 grid, this rank's entries (those of its blocks) on a 2D grid
             auto mine = [&](i64 e, int j) {
@@ -3714,6 +3843,15 @@ struct Plan : PlanBase {
             src = d_aval.p;
         }
         d_acur = src;
+        d_acur64 = nullptr;
+        fill_storage([&](unsigned blocks) {
+            hipLaunchKernelGGL(k_fill_a<T>, dim3(blocks), dim3(FILL_THREADS), 0, stream,
+                               d_amap.p, src, a_nnz, d_L.p, d_U.p);
+        });
+    }
+
+    // zero this rank's L and U, scatter A's values with `launch`; t_fill_ms
+    template <typename F> void fill_storage(F &&launch) {
         vstate = 1;
         host_current = false;
         hipEvent_t e0, e1;
@@ -3724,9 +3862,7 @@ struct Plan : PlanBase {
         if (d_L.n) HIPCHK(hipMemsetAsync(d_L.p, 0, d_L.bytes(), stream));
         if (d_U.n) HIPCHK(hipMemsetAsync(d_U.p, 0, d_U.bytes(), stream));
         if (a_nnz) {
-            const i64 blocks = std::min<i64>((a_nnz + FILL_THREADS - 1) / FILL_THREADS, 65536);
-            hipLaunchKernelGGL(k_fill_a<T>, dim3((unsigned)blocks), dim3(FILL_THREADS), 0, stream,
-                               d_amap.p, src, a_nnz, d_L.p, d_U.p);
+            launch((unsigned)std::min<i64>((a_nnz + FILL_THREADS - 1) / FILL_THREADS, 65536));
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(e1, stream));
@@ -3736,6 +3872,35 @@ struct Plan : PlanBase {
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
         stats.t_fill_ms = ms;
+    }
+
+    static const char *dtype_name() {
+        return std::is_same<T, float>::value ? "s (fp32)" : std::is_same<T, double>::value ? "d (fp64)" : "z (complex fp64)";
+    }
+
+    // fill_a of an fp32 plan from fp64 values: L / U get the rounded values
+    // in the one pass that reads the doubles, which stay on the device as the
+    // A of refine_d2's residual (no fp32 copy of A exists afterwards, so the
+    // plain refine refuses such factors).
+    void fill_a_d2(const double *a, int on_device) override {
+        if constexpr (std::is_same<T, float>::value) {
+            SLU_REQUIRE(a_nnz >= 0, "fill_a_d2 before set_a_pattern");
+            const double *src = a;
+            if (!on_device) {
+                if (d_aval64.n != (size_t)std::max<i64>(a_nnz, 1)) d_aval64.alloc(std::max<i64>(a_nnz, 1));
+                if (a_nnz)
+                    HIPCHK(hipMemcpyAsync(d_aval64.p, a, (size_t)a_nnz * sizeof(double), hipMemcpyHostToDevice, stream));
+                src = d_aval64.p;
+            }
+            d_acur = nullptr;
+            d_acur64 = src;
+            fill_storage([&](unsigned blocks) {
+                hipLaunchKernelGGL(k_fill_a_d2, dim3(blocks), dim3(FILL_THREADS), 0, stream,
+                                   d_amap.p, src, a_nnz, d_L.p, d_U.p);
+            });
+        } else {
+            throw Error(fmt("fill_a_d2: fp32 plans only, this plan's dtype is %s", dtype_name()));
+        }
     }
 
     // ---- helper threads of the plan build: the H2D copy of the values and
@@ -4005,6 +4170,19 @@ int slu_plan_refine(slu_plan *p, const void *b, void *x, int64_t ld, int nrhs, d
                     int *steps) {
     return guarded([&] {
         p->impl->refine(b, x, ld, nrhs, berr, steps);
+    });
+}
+
+int slu_plan_fill_a_d2(slu_plan *p, const double *a, int on_device) {
+    return guarded([&] {
+        p->impl->fill_a_d2(a, on_device);
+    });
+}
+
+int slu_plan_refine_d2(slu_plan *p, const double *b, double *x, int64_t ld, int nrhs, double *berr,
+                       int *steps) {
+    return guarded([&] {
+        p->impl->refine_d2(b, x, ld, nrhs, berr, steps);
     });
 }
 

@@ -98,6 +98,15 @@ struct CoarsePlan : PlanBase {
         in->refine(b, x, ld, nrhs, berr, steps);
         sync_stats();
     }
+    void fill_a_d2(const double *a, int on_device) override {
+        in->fill_a_d2(a, on_device);
+        coarse_changed();
+        sync_stats();
+    }
+    void refine_d2(const double *b, double *x, int64_t ld, int nrhs, double *berr, int *steps) override {
+        in->refine_d2(b, x, ld, nrhs, berr, steps);
+        sync_stats();
+    }
     void check_exchange(int64_t *nsec, int64_t *nbytes) override {
         in->check_exchange(nsec, nbytes);
         sync_stats();
@@ -527,6 +536,7 @@ struct AmalgPlan : CoarsePlan<T, HT, LocalLU, LUS> {
         t_expand = ms_since(t1);
         in->vstate = 1;
         in->d_acur = nullptr;
+        in->d_acur64 = nullptr;
         in->host_current = false;
         coarse_current = false;
         host_done = false;
@@ -537,6 +547,8 @@ struct AmalgPlan : CoarsePlan<T, HT, LocalLU, LUS> {
         upload();
         in->sync();
         in->vstate = 2;
+        in->a_fact = nullptr; // adopted factors: of no A this plan knows
+        in->a_fact64 = nullptr;
         coarse_current = true;
         host_done = true; // the caller's arrays hold these factors already
     }
@@ -812,6 +824,7 @@ struct GridAmalgPlan : CoarsePlan<T, HT, LocalLU, LUS> {
         expand();
         in->vstate = 1;
         in->d_acur = nullptr;
+        in->d_acur64 = nullptr;
         in->host_current = false;
         coarse_current = false;
         sync_stats();
@@ -820,6 +833,8 @@ struct GridAmalgPlan : CoarsePlan<T, HT, LocalLU, LUS> {
         upload();
         in->sync();
         in->vstate = 2;
+        in->a_fact = nullptr; // adopted factors: of no A this plan knows
+        in->a_fact64 = nullptr;
     }
     void factor(double anorm, int *info, int *tiny) override {
         in->factor(anorm, info, tiny);

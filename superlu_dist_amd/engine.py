@@ -232,6 +232,33 @@ class Plan:
                                         steps.ctypes.data_as(C.POINTER(C.c_int))))
         return xx, berr[:nrhs], steps[:nrhs]
 
+    def fill_a_d2(self, values):
+        """fp32 plans: fill_a from float64 values.  The factor storage gets
+        them rounded to float32; the float64 values stay on the device as the
+        A of refine_d2."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if len(v) != len(self._asub):
+            raise ValueError(f"{len(v)} values for a pattern of {len(self._asub)} nonzeros")
+        self._chk(lib().slu_plan_fill_a_d2(self.ptr, v.ctypes.data_as(C.c_void_p), 0))
+
+    def refine_d2(self, b, x):
+        """fp32 plans: mixed-precision refinement of x for A x = b, A = the
+        float64 values of the last fill_a_d2 (residual and update in float64,
+        corrections from the float32 factors); b, x float64, x = the initial
+        iterate (zeros allowed).  Returns (x, berr, steps) per column."""
+        bb = np.array(b, dtype=np.float64, order="F", copy=True)
+        xx = np.array(x, dtype=np.float64, order="F", copy=True)
+        if bb.shape != xx.shape:
+            raise ValueError("b and x differ in shape")
+        nrhs = 1 if bb.ndim == 1 else bb.shape[1]
+        berr = np.zeros(max(nrhs, 1))
+        steps = np.zeros(max(nrhs, 1), dtype=np.int32)
+        self._chk(lib().slu_plan_refine_d2(self.ptr, bb.ctypes.data_as(C.c_void_p),
+                                           xx.ctypes.data_as(C.c_void_p), bb.shape[0], nrhs,
+                                           berr.ctypes.data_as(C.POINTER(C.c_double)),
+                                           steps.ctypes.data_as(C.POINTER(C.c_int))))
+        return xx, berr[:nrhs], steps[:nrhs]
+
     def check_exchange(self):
         """Schedule-only plans: replay every level's exchange phases of
         factor() through the communicator, each received section checked

@@ -170,6 +170,9 @@ def lib():
         "slu_plan_set_a_pattern": (C.c_int, [P, C.c_int64, c_i64p, c_i64p]),
         "slu_plan_fill_a": (C.c_int, [P, P, C.c_int]),
         "slu_plan_refine": (C.c_int, [P, P, P, C.c_int64, C.c_int, C.POINTER(C.c_double), c_intp]),
+        "slu_plan_fill_a_d2": (C.c_int, [P, P, C.c_int]),
+        "slu_plan_refine_d2": (C.c_int, [P, P, P, C.c_int64, C.c_int, C.POINTER(C.c_double),
+                                         c_intp]),
         "slu_plan_snapshot": (C.c_int, [P]),
         "slu_plan_restore": (C.c_int, [P]),
         "slu_plan_sync": (C.c_int, [P]),
