@@ -266,6 +266,36 @@ int slu_plan_refine(slu_plan *p, const void *b, void *x, int64_t ld, int nrhs, d
 int slu_plan_fill_a_d2(slu_plan *p, const double *a, int on_device);
 int slu_plan_refine_d2(slu_plan *p, const double *b, double *x, int64_t ld, int nrhs,
                        double *berr, int *steps);
+/* Solves with the transpose on the same device factors (1x1 plans; 2D and
+ * 3D plans are refused: the distributed transposed sweep swaps the roles of
+ * process rows and columns).  The LUstruct factors
+ * B = Pc Pr diag(R) A diag(C) Pc^T; trans selects B y = c (SLU_NOTRANS,
+ * exactly slu_plan_solve / slu_plan_refine), B^T y = c (SLU_TRANS) or
+ * B^H y = c (SLU_CONJ; on a real plan the same as SLU_TRANS).  U^T z = c
+ * runs forward and L^T y = z backward over the factorization's own levels,
+ * with no storage beyond the factors.  A caller who starts from A:
+ *   A^T x = b  becomes  B^T y = c  with  c[perm_c[j]] = C[j] b[j],
+ *   and the solution comes back as  x[i] = R[i] y[perm_c[perm_r[i]]]
+ * (row i of A is row perm_c[perm_r[i]] of B, column j is column perm_c[j]).
+ * refine_t: the loop of slu_plan_refine on r = c - op(B)^T x,
+ * s = |B^T||x| + |c| (a row of B^T is a column of the CSC of
+ * slu_plan_set_a_pattern), same guards, stopping rule and refusals.
+ * t_solve_ms / t_refine_ms report the last call of either kind. */
+enum { SLU_NOTRANS = 0, SLU_TRANS = 1, SLU_CONJ = 2 };
+int slu_plan_solve_t(slu_plan *p, int trans, void *b, int64_t ldb, int nrhs);
+int slu_plan_refine_t(slu_plan *p, int trans, const void *b, void *x, int64_t ld, int nrhs,
+                      double *berr, int *steps);
+/* Reciprocal condition estimate of the factored B (1x1 plans), the number
+ * sequential SuperLU's dgscon returns: Hager / Higham's estimator of
+ * ||B^-1|| as in LAPACK dlacn2 / zlacn2, each step one sweep or transposed
+ * sweep of a single device vector; only scalars cross PCIe.  norm '1':
+ * ||B^-1||_1, 'I': ||B^-1||_inf; anorm = the same norm of B, computed by the
+ * caller.  *rcond = 1 / (anorm est), or 0 when anorm is 0 or est is not
+ * finite.  The estimate is a lower bound of the true norm, so rcond is an
+ * upper bound of the true reciprocal condition number.
+ * rcond_info: sweeps and device time (ms) of the last slu_plan_rcond. */
+int slu_plan_rcond(slu_plan *p, int norm /* '1' or 'I' */, double anorm, double *rcond);
+int slu_plan_rcond_info(const slu_plan *p, int *sweeps, double *ms);
 /* Schedule-only plans: replay every level's exchange phases of
  * slu_plan_factor through the communicator on host buffers; each received
  * section is checked byte for byte against what its root wrote.  Collective;
@@ -297,9 +327,9 @@ typedef struct {
     int64_t n_schur_big_launches;
     double comm_bytes;         /* bytes of the broadcast sections this rank
                                   takes part in (as root or receiver) per factor */
-    double t_solve_ms;         /* device time of the last slu_plan_solve */
+    double t_solve_ms;         /* device time of the last slu_plan_solve / solve_t */
     double t_fill_ms;          /* device time of the last slu_plan_fill_a */
-    double t_refine_ms;        /* device time of the last slu_plan_refine */
+    double t_refine_ms;        /* device time of the last slu_plan_refine / refine_t */
     /* host wall times of the drop-in path (ms) */
     double t_plan_ms;          /* slu_plan_create */
     double t_upload_ms;        /* H2D of the L/U values (overlapped with the

@@ -295,6 +295,13 @@ struct PlanBase {
     virtual void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) = 0;
     virtual void fill_a(const void *a, int on_device) = 0;
     virtual void refine(const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) = 0;
+    // B^T / B^H on the same factors (1x1 plans; solve.h), trans = SLU_TRANS / SLU_CONJ
+    virtual void solve_t(int trans, void *b, int64_t ldb, int nrhs) = 0;
+    virtual void refine_t(int trans, const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) = 0;
+    // reciprocal condition estimate; sweeps and device time of the call in rc_*
+    virtual void rcond(int norm, double anorm, double *rc) = 0;
+    int rc_sweeps = 0;
+    double rc_ms = 0;
     // fp32 plans: fp64 values of A, fp64 residual and update (refine_d2.h)
     virtual void fill_a_d2(const double *a, int on_device) = 0;
     virtual void refine_d2(const double *b, double *x, int64_t ld, int nrhs, double *berr, int *steps) = 0;
@@ -3183,6 +3190,50 @@ struct Plan : PlanBase {
         if (nr == 1) sweep_nr<1>(xv, ldx, 1);
         else sweep_nr<SvNr<T>::v>(xv, ldx, nr);
     }
+    // the transposed sweeps over the same levels and tables: U^T z = c
+    // ascending (solve, then push along U's rows), L^T y = z descending (pull
+    // down L's columns, then solve); conj: B^H (complex plans)
+    template <int NR> void sweep_t_nr(T *xv, i64 ldx, int nr, int conj) {
+        const int nl = (int)bylev.size();
+        for (int L = 0; L < nl; ++L) {
+            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_u_off[L + 1] - sv_u_off[L];
+            if (nd)
+                hipLaunchKernelGGL((k_sv_utdiag<T, NR>), dim3(nd), dim3(SVD_THREADS), 0, stream,
+                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xv, ldx, nr, conj);
+            if (nc)
+                hipLaunchKernelGGL((k_sv_utpanel<T, NR>), dim3(nc), dim3(SV_THREADS), 0, stream,
+                                   d_sv_uch.p + sv_u_off[L], d_sv_diag.p, d_sv_coff.p,
+                                   d_sv_ncol.p, d_ucol_voff.p, d_ucol_fst.p, d_sv_gc.p,
+                                   d_U.p, xv, ldx, nr, conj);
+        }
+        for (int L = nl - 1; L >= 0; --L) {
+            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_l_off[L + 1] - sv_l_off[L];
+            if (nc)
+                hipLaunchKernelGGL((k_sv_ltpanel<T, NR>), dim3(nc), dim3(SV_THREADS), 0, stream,
+                                   d_sv_lch.p + sv_l_off[L], d_sv_pan.p, d_sv_roff.p,
+                                   d_sv_rows.p, d_L.p, xv, ldx, nr, conj);
+            if (nd)
+                hipLaunchKernelGGL((k_sv_ltdiag<T, NR>), dim3(nd), dim3(SVD_THREADS), 0, stream,
+                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xv, ldx, nr, conj);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    void sweep_t(T *xv, int conj, i64 ldx = 0, int nr = 1) {
+        if (nr == 1) sweep_t_nr<1>(xv, ldx, 1, conj);
+        else sweep_t_nr<SvNr<T>::v>(xv, ldx, nr, conj);
+    }
+    // op(B)^-1 on the device vectors: trans 0 = B, 1 = B^T, 2 = B^H
+    void sweep_op(int trans, T *xv, i64 ldx = 0, int nr = 1) {
+        if (trans) sweep_t(xv, trans == SLU_CONJ, ldx, nr);
+        else sweep(xv, ldx, nr);
+    }
+    // what the transposed calls and rcond refuse (`what` names the call)
+    void require_1x1_factors(const char *what) {
+        SLU_REQUIRE(!zmode, "%s: not on 3D plans (the transposed sweep runs on 1x1 plans only)", what);
+        SLU_REQUIRE(!xmode, "%s: not on a %dx%d grid (the transposed sweep swaps the roles of process "
+                    "rows and columns; 1x1 plans only)", what, Pr, Pc);
+        SLU_REQUIRE(vstate == 2, "%s: the device storage holds no factors (factor first)", what);
+    }
 
     // ---- 2D grids: the distributed supernodal solve of pdgstrs
     // (SRC/pdgstrs.c, pdgstrs_lsum.c), level-scheduled.  Block row k's partial
@@ -3378,7 +3429,13 @@ struct Plan : PlanBase {
 
     // right-hand sides in batches of SvNr<T>: every factor element is read once
     // per batch and sweep
-    void solve(void *b, int64_t ldb, int nrhs) override {
+    void solve(void *b, int64_t ldb, int nrhs) override { solve_op(SLU_NOTRANS, b, ldb, nrhs); }
+    void solve_t(int trans, void *b, int64_t ldb, int nrhs) override {
+        SLU_REQUIRE(trans >= SLU_NOTRANS && trans <= SLU_CONJ, "solve_t: trans = %d is none of SLU_NOTRANS, SLU_TRANS, SLU_CONJ", trans);
+        if (trans != SLU_NOTRANS) require_1x1_factors("solve_t");
+        solve_op(trans, b, ldb, nrhs);
+    }
+    void solve_op(int trans, void *b, int64_t ldb, int nrhs) {
         SLU_REQUIRE(!zmode, "solve: 3D plans hold the factors spread over the layers (gather them to a 2D plan)");
         SLU_REQUIRE(vstate == 2, "solve: the device storage holds no factors (factor first)");
         if (!sv_ready) build_solve();
@@ -3419,7 +3476,7 @@ struct Plan : PlanBase {
                 HIPCHK(hipMemcpyAsync(d_sv_x.p + (i64)q * n, (HT *)b + (i64)(r0 + q) * ldb,
                                       (size_t)n * sizeof(T), hipMemcpyHostToDevice, stream));
             HIPCHK(hipEventRecord(e0, stream));
-            sweep(d_sv_x.p, n, nr);
+            sweep_op(trans, d_sv_x.p, n, nr);
             HIPCHK(hipEventRecord(e1, stream));
             for (int q = 0; q < nr; ++q)
                 HIPCHK(hipMemcpyAsync((HT *)b + (i64)(r0 + q) * ldb, d_sv_x.p + (i64)q * n,
@@ -3511,6 +3568,34 @@ struct Plan : PlanBase {
     }
 
     void refine(const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) override {
+        refine_op(SLU_NOTRANS, b, x, ld, nrhs, berr, steps);
+    }
+    void refine_t(int trans, const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) override {
+        SLU_REQUIRE(trans >= SLU_NOTRANS && trans <= SLU_CONJ, "refine_t: trans = %d is none of SLU_NOTRANS, SLU_TRANS, SLU_CONJ", trans);
+        if (trans != SLU_NOTRANS) require_1x1_factors("refine_t");
+        refine_op(trans, b, x, ld, nrhs, berr, steps);
+    }
+
+    // The CSC view of A for the transposed residual (k_resid_t), made on the
+    // device from the rows of set_a_pattern at the first transposed refine.
+    bool csc_ready = false;
+    DevBuf<int> d_csc_ci;
+    DevBuf<unsigned long long> d_csc_lo, d_csc_hi;
+    void build_csc() {
+        const size_t nn = (size_t)std::max(n, 1);
+        d_csc_ci.alloc(std::max<i64>(a_nnz, 1));
+        d_csc_lo.alloc(nn);
+        d_csc_hi.alloc(nn);
+        HIPCHK(hipMemsetAsync(d_csc_lo.p, 0xff, nn * sizeof(unsigned long long), stream));
+        HIPCHK(hipMemsetAsync(d_csc_hi.p, 0, nn * sizeof(unsigned long long), stream));
+        if (n)
+            hipLaunchKernelGGL(k_csc_of_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                               d_rp.p, d_rc.p, d_re.p, n, d_csc_ci.p, d_csc_lo.p, d_csc_hi.p);
+        HIPCHK(hipGetLastError());
+        csc_ready = true;
+    }
+
+    void refine_op(int trans, const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) {
         SLU_REQUIRE(!zmode, "refine: not on 3D plans");
         SLU_REQUIRE(vstate == 2, "refine: the device storage holds no factors (factor first)");
         SLU_REQUIRE(a_fact != nullptr,
@@ -3527,6 +3612,7 @@ struct Plan : PlanBase {
         d_rf_r.alloc(std::max(n, 1));
         d_rf_berr.alloc(1);
         if (xmode && rf_rows_h.empty() && rf_secs.empty()) build_refine_2d();
+        if (trans && !csc_ready) build_csc();
         const unsigned rb = (unsigned)((n + 255) / 256);
         hipEvent_t e0, e1;
         HIPCHK(hipEventCreate(&e0));
@@ -3545,8 +3631,13 @@ struct Plan : PlanBase {
                     be = resid_2d(safe1, safe2);
                 } else {
                     HIPCHK(hipMemsetAsync(d_rf_berr.p, 0, sizeof(unsigned long long), stream));
-                    hipLaunchKernelGGL(k_resid<T>, dim3(rb), dim3(256), 0, stream, d_rp.p, d_rc.p, d_re.p,
-                                       a_fact, d_rf_x.p, d_rf_b.p, d_rf_r.p, n, safe1, safe2, d_rf_berr.p);
+                    if (trans)
+                        hipLaunchKernelGGL(k_resid_t<T>, dim3(rb), dim3(256), 0, stream, d_csc_lo.p, d_csc_hi.p,
+                                           d_csc_ci.p, a_fact, d_rf_x.p, d_rf_b.p, d_rf_r.p, n, safe1, safe2,
+                                           d_rf_berr.p, (int)(trans == SLU_CONJ));
+                    else
+                        hipLaunchKernelGGL(k_resid<T>, dim3(rb), dim3(256), 0, stream, d_rp.p, d_rc.p, d_re.p,
+                                           a_fact, d_rf_x.p, d_rf_b.p, d_rf_r.p, n, safe1, safe2, d_rf_berr.p);
                     HIPCHK(hipGetLastError());
                     unsigned long long bits = 0;
                     HIPCHK(hipMemcpyAsync(&bits, d_rf_berr.p, sizeof bits, hipMemcpyDeviceToHost, stream));
@@ -3558,7 +3649,7 @@ struct Plan : PlanBase {
                     sv_gather(d_rf_r.p); // R from its owners to every rank, then the 2D solve
                     sweep_2d(d_rf_r.p);
                 } else {
-                    sweep(d_rf_r.p);
+                    sweep_op(trans, d_rf_r.p);
                 }
                 hipLaunchKernelGGL(k_axpy1<T>, dim3(rb), dim3(256), 0, stream, d_rf_x.p, d_rf_r.p, n);
                 lstres = be;
@@ -3692,6 +3783,107 @@ struct Plan : PlanBase {
         }
     }
 
+    // Reciprocal condition estimate of the factored B, what sequential
+    // SuperLU's dgscon returns: Hager / Higham's 1-norm estimator of B^-1 as
+    // in LAPACK dlacn2 / zlacn2 (sign vector, first-maximum index, at most 5
+    // iterations, the alternating-sign final vector), the host loop over one
+    // device vector.  Each step is one sweep (B^-1, kase 1) or transposed
+    // sweep (B^-H, kase 2) plus a one-workgroup kernel; RcOut is all that
+    // crosses PCIe.  norm 'I' swaps the two (||B^-1||_inf = ||B^-H||_1).
+    DevBuf<T> d_rc_x, d_rc_sgn;
+    DevBuf<RcOut> d_rc_out;
+    void rcond(int norm, double anorm, double *rc) override {
+        const bool one = norm == '1' || norm == 'O' || norm == 'o';
+        SLU_REQUIRE(one || norm == 'I' || norm == 'i', "rcond: norm is '1' or 'I', not %d", norm);
+        SLU_REQUIRE(rc != nullptr, "rcond: no place for the result");
+        require_1x1_factors("rcond");
+        if (!sv_ready) build_solve();
+        const bool real = sizeof(T) != sizeof(zc);
+        const int adj = real ? SLU_TRANS : SLU_CONJ;
+        const int op1 = one ? SLU_NOTRANS : adj, op2 = one ? adj : SLU_NOTRANS;
+        const size_t nn = (size_t)std::max(n, 1);
+        if (d_rc_x.n != nn) {
+            d_rc_x.alloc(nn);
+            d_rc_sgn.alloc(nn);
+            d_rc_out.alloc(1);
+        }
+        const unsigned fb = (unsigned)((n + 255) / 256);
+        int sweeps = 0;
+        auto fill = [&](int mode, int j) {
+            if (n) hipLaunchKernelGGL(k_rc_fill<T>, dim3(fb), dim3(256), 0, stream, d_rc_x.p, n, mode, j);
+        };
+        auto apply = [&](int op) {
+            sweep_op(op, d_rc_x.p);
+            ++sweeps;
+        };
+        auto fetch = [&]() {
+            RcOut o;
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(&o, d_rc_out.p, sizeof o, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            return o;
+        };
+        auto norm_sign = [&](int dosign) {
+            hipLaunchKernelGGL(k_rc_norm_sign<T>, dim3(1), dim3(RC_THREADS), 0, stream, d_rc_x.p,
+                               d_rc_sgn.p, n, dosign, d_rc_out.p);
+            return fetch();
+        };
+        auto amax = [&](int jlast) {
+            hipLaunchKernelGGL(k_rc_amax<T>, dim3(1), dim3(RC_THREADS), 0, stream, (const T *)d_rc_x.p, n,
+                               jlast, d_rc_out.p);
+            return fetch();
+        };
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        HIPCHK(hipStreamSynchronize(pstream));
+        HIPCHK(hipEventRecord(e0, stream));
+        HIPCHK(hipMemsetAsync(d_rc_sgn.p, 0, nn * sizeof(T), stream));
+        double est = 0.0;
+        bool ok = n > 0;
+        if (ok) {
+            fill(0, 0);
+            apply(op1);
+            est = norm_sign(n > 1).sum;
+            ok = std::isfinite(est);
+        }
+        if (ok && n > 1) {
+            apply(op2);
+            int j = amax(-1).j;
+            for (int iter = 2; ok && j < n;) {
+                fill(1, j);
+                apply(op1);
+                const double estold = est;
+                const RcOut o = norm_sign(1);
+                est = o.sum;
+                ok = std::isfinite(est);
+                // a repeated sign vector (real) or no growth: converged
+                if (!ok || (real && o.ndiff == 0) || est <= estold) break;
+                apply(op2);
+                const RcOut m = amax(j);
+                j = m.j;
+                if (!(m.xlast != m.amax && iter < 5)) break;
+                ++iter;
+            }
+            if (ok) { // the alternating-sign vector catches what the iteration cancels
+                fill(2, 0);
+                apply(op1);
+                const double temp = 2.0 * (norm_sign(0).sum / (3.0 * n));
+                ok = std::isfinite(temp);
+                if (temp > est) est = temp;
+            }
+        }
+        HIPCHK(hipEventRecord(e1, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        rc_sweeps = sweeps;
+        rc_ms = ms;
+        *rc = (ok && anorm != 0.0 && std::isfinite(anorm) && est != 0.0) ? 1.0 / (anorm * est) : 0.0;
+    }
+
     // ------------------------------------------------------- values of A
     // SamePattern_SameRowPerm refill (SRC/pddistribute.c:545-672) on the
     // device: the destination of every nonzero of A in this rank's L/U
@@ -3770,6 +3962,7 @@ struct Plan : PlanBase {
         a_nnz = nnz;
         d_acur = a_fact = snap_acur = nullptr; // the previous pattern's values are gone
         d_acur64 = a_fact64 = snap_acur64 = nullptr;
+        csc_ready = false;
         {   // rows of A for the refinement's residual (k_resid): all of A on a
             // 1x1 grid, this rank's entries (those of its blocks) on a 2D grid
             auto mine = [&](i64 e, int j) {
@@ -4171,6 +4364,31 @@ int slu_plan_refine(slu_plan *p, const void *b, void *x, int64_t ld, int nrhs, d
     return guarded([&] {
         p->impl->refine(b, x, ld, nrhs, berr, steps);
     });
+}
+
+int slu_plan_solve_t(slu_plan *p, int trans, void *b, int64_t ldb, int nrhs) {
+    return guarded([&] {
+        p->impl->solve_t(trans, b, ldb, nrhs);
+    });
+}
+
+int slu_plan_refine_t(slu_plan *p, int trans, const void *b, void *x, int64_t ld, int nrhs,
+                      double *berr, int *steps) {
+    return guarded([&] {
+        p->impl->refine_t(trans, b, x, ld, nrhs, berr, steps);
+    });
+}
+
+int slu_plan_rcond(slu_plan *p, int norm, double anorm, double *rcond) {
+    return guarded([&] {
+        p->impl->rcond(norm, anorm, rcond);
+    });
+}
+
+int slu_plan_rcond_info(const slu_plan *p, int *sweeps, double *ms) {
+    if (sweeps) *sweeps = p->impl->rc_sweeps;
+    if (ms) *ms = p->impl->rc_ms;
+    return 0;
 }
 
 int slu_plan_fill_a_d2(slu_plan *p, const double *a, int on_device) {

@@ -98,6 +98,19 @@ struct CoarsePlan : PlanBase {
         in->refine(b, x, ld, nrhs, berr, steps);
         sync_stats();
     }
+    void solve_t(int trans, void *b, int64_t ldb, int nrhs) override {
+        in->solve_t(trans, b, ldb, nrhs);
+        sync_stats();
+    }
+    void refine_t(int trans, const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) override {
+        in->refine_t(trans, b, x, ld, nrhs, berr, steps);
+        sync_stats();
+    }
+    void rcond(int norm, double anorm, double *rc) override {
+        in->rcond(norm, anorm, rc);
+        rc_sweeps = in->rc_sweeps;
+        rc_ms = in->rc_ms;
+    }
     void fill_a_d2(const double *a, int on_device) override {
         in->fill_a_d2(a, on_device);
         coarse_changed();

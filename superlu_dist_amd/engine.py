@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from .lib import HOST_BCAST_FN, HOST_P2P_FN, EngineOpts, PlanStats, as_i64p, lib
+from .lib import HOST_BCAST_FN, HOST_P2P_FN, TRANS_CODE, EngineOpts, PlanStats, as_i64p, lib
 
 SMACH_EPS = 5.9604644775390625e-08  # smach_dist("Epsilon"), SRC/smach_dist.c:64
 
@@ -189,15 +189,30 @@ class Plan:
     def download(self):
         self._chk(lib().slu_plan_download(self.ptr))
 
-    def solve(self, b):
+    @staticmethod
+    def _trans(trans):
+        """'N' / 'T' / 'C' (or the SLU_* code itself) -> the code of the C API."""
+        if isinstance(trans, str):
+            if trans.upper() not in TRANS_CODE:
+                raise ValueError(f"trans = {trans!r}: one of 'N', 'T', 'C'")
+            return TRANS_CODE[trans.upper()]
+        return int(trans)
+
+    def solve(self, b, trans="N"):
         """Solve L U x = b with the device-resident factors (the LUstruct's
         permuted coordinates); b: (n,) or (n, nrhs).  Returns x.  On a 2D grid
-        every rank calls it with the same b and receives the whole x."""
+        every rank calls it with the same b and receives the whole x.
+        trans="T" / "C" solves with the transpose / conjugate transpose of the
+        factored matrix on the same factors (1x1 plans)."""
         dt = self.lu.Lval.dtype
         x = np.array(b, dtype=dt, order="F", copy=True)
         nrhs = 1 if x.ndim == 1 else x.shape[1]
         n = x.shape[0]
-        self._chk(lib().slu_plan_solve(self.ptr, x.ctypes.data_as(C.c_void_p), n, nrhs))
+        if trans == "N":
+            self._chk(lib().slu_plan_solve(self.ptr, x.ctypes.data_as(C.c_void_p), n, nrhs))
+        else:
+            self._chk(lib().slu_plan_solve_t(self.ptr, self._trans(trans),
+                                             x.ctypes.data_as(C.c_void_p), n, nrhs))
         return x
 
     def set_a_pattern(self, colptr, rowind):
@@ -215,9 +230,10 @@ class Plan:
             raise ValueError(f"{len(v)} values for a pattern of {len(self._asub)} nonzeros")
         self._chk(lib().slu_plan_fill_a(self.ptr, v.ctypes.data_as(C.c_void_p), 0))
 
-    def refine(self, b, x):
+    def refine(self, b, x, trans="N"):
         """Iterative refinement of x for A x = b on the device (pdgsrfs), A =
-        the values of the last fill_a; returns (x, berr, steps) per column."""
+        the values of the last fill_a; returns (x, berr, steps) per column.
+        trans="T" / "C": for A^T x = b / A^H x = b (1x1 plans)."""
         dt = self.lu.Lval.dtype
         bb = np.array(b, dtype=dt, order="F", copy=True)
         xx = np.array(x, dtype=dt, order="F", copy=True)
@@ -226,11 +242,29 @@ class Plan:
         nrhs = 1 if bb.ndim == 1 else bb.shape[1]
         berr = np.zeros(max(nrhs, 1))
         steps = np.zeros(max(nrhs, 1), dtype=np.int32)
-        self._chk(lib().slu_plan_refine(self.ptr, bb.ctypes.data_as(C.c_void_p),
-                                        xx.ctypes.data_as(C.c_void_p), bb.shape[0], nrhs,
-                                        berr.ctypes.data_as(C.POINTER(C.c_double)),
-                                        steps.ctypes.data_as(C.POINTER(C.c_int))))
+        args = (bb.ctypes.data_as(C.c_void_p), xx.ctypes.data_as(C.c_void_p), bb.shape[0], nrhs,
+                berr.ctypes.data_as(C.POINTER(C.c_double)), steps.ctypes.data_as(C.POINTER(C.c_int)))
+        if trans == "N":
+            self._chk(lib().slu_plan_refine(self.ptr, *args))
+        else:
+            self._chk(lib().slu_plan_refine_t(self.ptr, self._trans(trans), *args))
         return xx, berr[:nrhs], steps[:nrhs]
+
+    def rcond(self, anorm, norm="1"):
+        """Reciprocal condition estimate 1 / (anorm ||B^-1||) of the factored
+        matrix B (what SuperLU's dgscon returns; Hager / Higham's estimator
+        on the device factors).  norm "1" or "I"; anorm: the same norm of B."""
+        if norm not in ("1", "O", "I"):
+            raise ValueError(f"norm = {norm!r}: '1' or 'I'")
+        rc = C.c_double()
+        self._chk(lib().slu_plan_rcond(self.ptr, ord(norm), float(anorm), C.byref(rc)))
+        return rc.value
+
+    def rcond_info(self):
+        """(sweeps, device ms) of the last rcond()."""
+        k, ms = C.c_int(), C.c_double()
+        lib().slu_plan_rcond_info(self.ptr, C.byref(k), C.byref(ms))
+        return k.value, ms.value
 
     def fill_a_d2(self, values):
         """fp32 plans: fill_a from float64 values.  The factor storage gets

@@ -21,6 +21,8 @@ DROPIN_PATH = os.path.join(os.path.dirname(LIB_PATH), "libslu_mi355x.so")
 SLU_D, SLU_S, SLU_Z = 0, 1, 2
 DTYPES = {SLU_D: np.float64, SLU_S: np.float32, SLU_Z: np.complex128}
 DTYPE_CODE = {"d": SLU_D, "s": SLU_S, "z": SLU_Z}
+SLU_NOTRANS, SLU_TRANS, SLU_CONJ = 0, 1, 2
+TRANS_CODE = {"N": SLU_NOTRANS, "T": SLU_TRANS, "C": SLU_CONJ}
 
 c_i64p = C.POINTER(C.c_int64)
 c_intp = C.POINTER(C.c_int)
@@ -170,6 +172,11 @@ def lib():
         "slu_plan_set_a_pattern": (C.c_int, [P, C.c_int64, c_i64p, c_i64p]),
         "slu_plan_fill_a": (C.c_int, [P, P, C.c_int]),
         "slu_plan_refine": (C.c_int, [P, P, P, C.c_int64, C.c_int, C.POINTER(C.c_double), c_intp]),
+        "slu_plan_solve_t": (C.c_int, [P, C.c_int, P, C.c_int64, C.c_int]),
+        "slu_plan_refine_t": (C.c_int, [P, C.c_int, P, P, C.c_int64, C.c_int,
+                                        C.POINTER(C.c_double), c_intp]),
+        "slu_plan_rcond": (C.c_int, [P, C.c_int, C.c_double, C.POINTER(C.c_double)]),
+        "slu_plan_rcond_info": (C.c_int, [P, c_intp, C.POINTER(C.c_double)]),
         "slu_plan_fill_a_d2": (C.c_int, [P, P, C.c_int]),
         "slu_plan_refine_d2": (C.c_int, [P, P, P, C.c_int64, C.c_int, C.POINTER(C.c_double),
                                          c_intp]),
