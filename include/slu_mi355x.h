@@ -363,7 +363,9 @@ int slu_plan_get_stats(const slu_plan *p, slu_plan_stats *st);
  *   diag_generic, diag_f, diag_f_small, diag_wave32, diag_wave64, diag_strips,
  *   trsm_reg64_pf, trsm_reg64_nopf, trsm_reg128_pf, trsm_reg128_nopf,
  *   trsm_reg256_pf, trsm_reg256_nopf, trsm_blk, trsm_generic,
- *   schur_big, schur_small, ksplit_kinfos (KInfo's of K-split updates)
+ *   schur_big, schur_small, ksplit_kinfos (KInfo's of K-split updates),
+ *   schur_pairs, schur_fused_tiles (chained supernode pairs of the plan and the
+ *   128x128 tile pairs they run as one, SLU_SCHUR_PAIR)
  * and returns how many there are. */
 int slu_plan_path_counts(const slu_plan *p, int64_t *out, int n);
 

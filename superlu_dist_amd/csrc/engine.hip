@@ -81,6 +81,7 @@ struct LevelRange {
     int ps_off = 0, ps_n = 0;   // panel broadcasts
     double schur_flops = 0, big_flops = 0;
     int atomic_tiles = 0; // tiles of supernodes whose destinations collide within the level
+    int fused_n = 0;      // big tiles that carry a deferred tile of the level below as a first K segment
     bool big = false;
     // 2D grids: the level's panel exchange in nch chunks (Plan::pchunks).
     // Chunk c = row group c of every L panel and column group c of every U
@@ -211,15 +212,15 @@ struct FactorTimer {
             stats.t_zreduce_ms += ms(zmarks[i][1], zmarks[i][2]);
         }
         if (timing >= 2) { // per-level breakdown (stderr)
-            fprintf(stderr, "[slu rank %d] lvl nsup diag trsm big small atomic  GFLOP  diag_ms trsm_ms big_ms small_ms comm_ms  TF/s wall_ms\n", iam);
+            fprintf(stderr, "[slu rank %d] lvl nsup diag trsm big small atomic  GFLOP  diag_ms trsm_ms big_ms small_ms comm_ms  TF/s wall_ms fused\n", iam);
             for (size_t L = 0; L < levels.size(); ++L) {
                 const LevelRange &R = levels[L];
                 double sch = t[L][2] + t[L][3];
                 const float wall = ms(L ? lvl_end[L - 1] : e_start, lvl_end[L]);
-                fprintf(stderr, "[slu rank %d] %3zu %5zu %4d %5d %5d %5d %6d %7.2f %8.3f %7.3f %7.3f %7.3f %7.3f %6.2f %7.3f\n",
+                fprintf(stderr, "[slu rank %d] %3zu %5zu %4d %5d %5d %5d %6d %7.2f %8.3f %7.3f %7.3f %7.3f %7.3f %6.2f %7.3f %5d\n",
                         iam, L, bylev[L].size(), R.diag_n + R.df_n, R.lf_n + R.uf_n + R.tl_n + R.tu_n,
                         R.big_n, R.tile_n, R.atomic_tiles, R.schur_flops / 1e9, t[L][0], t[L][1], t[L][2], t[L][3],
-                        t[L][4], sch > 0 ? R.schur_flops / sch / 1e9 : 0.0, (double)wall);
+                        t[L][4], sch > 0 ? R.schur_flops / sch / 1e9 : 0.0, (double)wall, R.fused_n);
             }
         }
         reset(0);
@@ -312,12 +313,13 @@ struct PlanBase {
     // kernel launches of the last factor() by dispatch path (host-side counts
     // at the launch sites, slu_plan_path_counts; the order is the ABI):
     // the diagonal kernels, k_trsm_reg per width and PF form, k_trsm_blk,
-    // k_trsm_l / k_trsm_u, the Schur kernels, and the KInfo's of K-split updates
+    // k_trsm_l / k_trsm_u, the Schur kernels, the KInfo's of K-split updates,
+    // and the plan's chained pairs with the tile pairs they fuse (SLU_SCHUR_PAIR)
     enum PathCount {
         PC_DIAG_GENERIC, PC_DIAG_F, PC_DIAG_F_SMALL, PC_DIAG_WAVE32, PC_DIAG_WAVE64, PC_DIAG_STRIPS,
         PC_TRSM_REG64_PF, PC_TRSM_REG64_NOPF, PC_TRSM_REG128_PF, PC_TRSM_REG128_NOPF,
         PC_TRSM_REG256_PF, PC_TRSM_REG256_NOPF, PC_TRSM_BLK, PC_TRSM_GENERIC,
-        PC_SCHUR_BIG, PC_SCHUR_SMALL, PC_KSPLIT_KINFOS, PC_N
+        PC_SCHUR_BIG, PC_SCHUR_SMALL, PC_KSPLIT_KINFOS, PC_SCHUR_PAIRS, PC_SCHUR_FUSED_TILES, PC_N
     };
     int64_t path_counts[PC_N] = {};
 };
@@ -609,11 +611,18 @@ struct Plan : PlanBase {
         layout_values();
         tick("layout_values");
         if (zmode) build_zranges(true);
+        build_pairs();
         build_schedule();
         if (prof)
             fprintf(stderr, "[slu plan %d]   (add_supernode %.1f ms, merge + atomics %.1f ms: "
                             "resize %.1f, copy %.1f, tiles %.1f)\n",
                     iam, t_addsn, t_merge, t_resize, t_put, t_tiles);
+        if (prof && n_pairs) {
+            double bigf = 0;
+            for (auto &R : levels) bigf += R.big_flops;
+            fprintf(stderr, "[slu plan %d]   (chained pairs %lld, fused tiles %lld, %.1f %% of the big-tile flops)\n", iam,
+                    (long long)n_pairs, (long long)n_fused_tiles, bigf > 0 ? 100.0 * fused_flops / bigf : 0.0);
+        }
         tick("build_schedule");
         join_streams();
         build_device();
@@ -1712,10 +1721,104 @@ struct Plan : PlanBase {
         double R_schur_flops = 0, R_big_flops = 0;
         i64 n_diag = 0, n_trsm_items = 0, n_schur_tiles = 0;
         i64 n_ksplit = 0; // KInfo's of updates whose K range is split (SLU_KSPLIT_TILES)
+        i64 n_fused = 0;  // tiles that carry a pair's first member as a first K segment
+        double fused_flops = 0; // flops of those first segments
+        vector<std::pair<int, int>> far_slots; // (first member of a pair, slot of its far KInfo)
         bool R_big = false;
     };
     vector<KInfoHost> khost;
     i64 n_ksplit_kinfos = 0;
+
+    // ------------------------------------------------------- chained pairs
+    // SLU_SCHUR_PAIR (default 1): supernode k and its parent k' one level up
+    // form a pair where the rows and U columns of k beyond block k' are
+    // exactly the rows and U columns of k' (consecutive members of one
+    // separator's chain).  The far x far part of k's update then covers, tile
+    // for tile, the update of k'; where the tile of k' is a rest tile, k's is
+    // left out at its own level and runs one level later as a first K segment
+    // of the tile of k' (TileItem::seg): one prologue and one scatter for
+    // both.  Its destinations belong to panels at least three levels up, so
+    // nothing reads them before.  Plans of one process only; 0 plans today's
+    // schedule exactly.
+    int schur_pair = env_int("SLU_SCHUR_PAIR", 1);
+    vector<int> pair_next, pair_prev; // the other member of k's pair, or -1
+    vector<int> far_kinfo;            // first members: index of the far part's KInfo
+    i64 n_pairs = 0, n_fused_tiles = 0;
+    double fused_flops = 0; // flops that run as first segments of fused tiles
+    static constexpr int SEG_PENDING = INT_MIN; // TileItem::seg = SEG_PENDING + k until the merge
+
+    // rows of L(:,k) below the diagonal block: global index and block of each
+    void sn_rows(int k, vector<int> &rg, vector<int> &rblk) const {
+        rg.clear();
+        rblk.clear();
+        const int_t *ix = lidx[k];
+        i64 p = SLU_BC_HEADER;
+        for (i64 b = 0; b < ix[0]; ++b) {
+            const int gb = (int)ix[p], nr = (int)ix[p + 1];
+            for (int i = 0; gb != k && i < nr; ++i) {
+                rg.push_back((int)ix[p + 2 + i]);
+                rblk.push_back(gb);
+            }
+            p += SLU_LB_DESCRIPTOR + nr;
+        }
+    }
+    // nonempty columns of U(k,:): global index, block and segment start of each
+    void sn_cols(int k, vector<int> &cg, vector<int> &cblk, vector<int> &t0) const {
+        cg.clear();
+        cblk.clear();
+        t0.clear();
+        const int_t *ix = uidx[k];
+        const i64 klst = xsup[k + 1];
+        i64 p = SLU_BR_HEADER;
+        for (i64 b = 0; b < ix[0]; ++b) {
+            const int jb = (int)ix[p];
+            for (int c = 0; c < W(jb); ++c) {
+                const i64 fst = ix[p + SLU_UB_DESCRIPTOR + c];
+                if (fst >= klst) continue;
+                cg.push_back((int)xsup[jb] + c);
+                cblk.push_back(jb);
+                t0.push_back((int)(fst - xsup[k]));
+            }
+            p += SLU_UB_DESCRIPTOR + W(jb);
+        }
+    }
+    void build_pairs() {
+        pair_next.assign(nsupers, -1);
+        pair_prev.assign(nsupers, -1);
+        far_kinfo.assign(nsupers, -1);
+        if (!schur_pair || xmode || zmode) return;
+        constexpr int BBN = BigCfg<T>::BN;
+        // (an update that SLU_KSPLIT_TILES may split is left alone)
+        auto may_split = [&](int k) { return ksplit_tiles > 0 && bylev[level_of[k]].size() <= 2; };
+        vector<int> rg, rb, cg, cb, t0, rg2, rb2, cg2, cb2, t02;
+        // ascending k: along a chain greedily from its first member
+        for (int k = 0; k < nsupers; ++k) {
+            if (pair_prev[k] >= 0 || !lidx[k] || !uidx[k] || may_split(k)) continue;
+            int m = 0, r0 = 0;
+            lrows(k, m, r0);
+            if (m < SB_BM) continue;
+            sn_rows(k, rg, rb);
+            sn_cols(k, cg, cb, t0);
+            const int n_ = (int)cg.size();
+            if (n_ < BBN) continue;
+            const int kp = rb[0];
+            if (cb[0] != kp || level_of[kp] != level_of[k] + 1 || pair_prev[kp] >= 0) continue;
+            if (!lidx[kp] || !uidx[kp] || may_split(kp)) continue;
+            int nr0 = 0, nc0 = 0;
+            while (nr0 < m && rb[nr0] == kp) ++nr0;
+            while (nc0 < n_ && cb[nc0] == kp) ++nc0;
+            if (m - nr0 < SB_BM || n_ - nc0 < BBN) continue; // k' runs big tiles too
+            sn_rows(kp, rg2, rb2);
+            sn_cols(kp, cg2, cb2, t02);
+            if ((int)rg2.size() != m - nr0 || (int)cg2.size() != n_ - nc0) continue;
+            if (!std::equal(rg2.begin(), rg2.end(), rg.begin() + nr0) ||
+                !std::equal(cg2.begin(), cg2.end(), cg.begin() + nc0))
+                continue;
+            pair_next[k] = kp;
+            pair_prev[kp] = k;
+            ++n_pairs;
+        }
+    }
 
     template <typename V> static void append(V &dst, const V &src) {
         dst.insert(dst.end(), src.begin(), src.end());
@@ -1778,6 +1881,8 @@ struct Plan : PlanBase {
                 b[V_PAIR] += O.h_pair.size();
             }
             base[NC] = b;
+            for (int t = 0; t < NC; ++t)
+                for (const auto &fs : outs[t].far_slots) far_kinfo[fs.first] = (int)base[t][V_K] + fs.second;
             diag_items.resize(b[V_DIAG]);
             df_items.resize(b[V_DF]);
             tl_items.resize(b[V_TL]);
@@ -1894,6 +1999,9 @@ struct Plan : PlanBase {
                 stats.n_trsm_items += O.n_trsm_items;
                 stats.n_schur_tiles += O.n_schur_tiles;
                 n_ksplit_kinfos += O.n_ksplit;
+                n_fused_tiles += O.n_fused;
+                fused_flops += O.fused_flops;
+                R.fused_n += (int)O.n_fused;
                 R.schur_flops += O.R_schur_flops;
                 R.big_flops += O.R_big_flops;
                 R.big = R.big || O.R_big;
@@ -1911,10 +2019,19 @@ struct Plan : PlanBase {
                         const int kb = (int)(base[t][V_K] - R.k_off);
                         for (TileItem x : outs[t].big[cls][ch]) {
                             x.kslot += kb;
+                            if (x.seg < SEG_PENDING + nsupers) { // fused: the first member's far KInfo
+                                const int fk = far_kinfo[x.seg - SEG_PENDING];
+                                SLU_REQUIRE(fk >= 0 && fk < R.k_off, "level %d: fused tile without its first segment", L);
+                                x.seg = fk - R.k_off;
+                            } else {
+                                x.seg += kb;
+                            }
                             tiles_big.push_back(x);
                         }
                         for (TileItem x : outs[t].small[cls][ch]) {
+                            SLU_REQUIRE(x.seg >= 0, "level %d: a 64x64 tile with a deferred first segment", L);
                             x.kslot += kb;
+                            x.seg = x.kslot;
                             tiles.push_back(x);
                         }
                     }
@@ -1929,6 +2046,15 @@ struct Plan : PlanBase {
                 if (cls == 0) {
                     R.bigc_n = bo[R.nch];
                     R.tilec_n = so[R.nch];
+                } else if (R.fused_n > 0) {
+                    // the fused tiles last among the rest tiles: they go out
+                    // as a launch of the two-segment kernel (one-process
+                    // plans only: one chunk)
+                    SLU_REQUIRE(!xmode && R.nch == 1, "level %d: fused tiles on a grid", L);
+                    auto e = std::stable_partition(tiles_big.begin() + b0, tiles_big.end(),
+                                                   [](const TileItem &x) { return x.seg == x.kslot; });
+                    SLU_REQUIRE(tiles_big.end() - e == R.fused_n, "level %d: %d fused tiles, %d counted", L,
+                                (int)(tiles_big.end() - e), R.fused_n);
                 }
             }
             R.big_n = (int)tiles_big.size() - R.big_off;
@@ -2192,7 +2318,83 @@ struct Plan : PlanBase {
         // ld = its rows), the tiles of a group in the exchange chunk of their
         // rows and columns
         const int gs = xmode ? lgsz[k] : m, ng = xmode ? ngroups(m, gs) : 1;
-        for (int g = 0; g < ng; ++g) {
+        const double mult = cplx ? 4.0 : 1.0; // complex: 8 real flops per multiply-add
+        // ---- a pair's members (build_pairs)
+        const int knext = pair_next[k], kprev = pair_prev[k];
+        vector<int> pcg, pcb, pt0; // second member: the first member's columns
+        double fl_fused = 0, fl_deferred = 0, el_deferred = 0;
+        double fl_small = 0; // first member: flops of the parts that run 64x64 tiles
+        i64 ntiles = (i64)tm * tn;
+        if (kprev >= 0) sn_cols(kprev, pcg, pcb, pt0);
+        if (knext >= 0) {
+            // First member: the update in three parts, each a KInfo with a
+            // tile grid of its own: near rows x all columns, far rows x near
+            // columns (destinations in the panels of k': critical), and far
+            // x far from (nr0, nc0), whose tiles coincide with the tiles of
+            // k'.  A far tile is deferred to the twin tile of k' where that
+            // one is a rest tile; it runs here, as before, where the twin is
+            // critical (destinations in the panels two levels up).
+            int nr0 = 0, nc0 = 0;
+            while (nr0 < m && lib_[O.h_ra[rows_off + nr0]] == knext) ++nr0;
+            while (nc0 < ncols && ujb[O.h_cb[cols_off + nc0]] == knext) ++nc0;
+            const int part[3][4] = {{0, 0, nr0, ncols}, {nr0, 0, m - nr0, nc0}, {nr0, nc0, m - nr0, ncols - nc0}};
+            ntiles = 0;
+            for (int pi = 0; pi < 3; ++pi) {
+                const int pr0 = part[pi][0], pc0 = part[pi][1], pm = part[pi][2], pn = part[pi][3];
+                if (pm <= 0 || pn <= 0) continue;
+                KInfo<T> kc = ki;
+                kc.a = d_L.p + lval_off[ljb] + r0 + pr0;
+                kc.lda = lval_ld[ljb];
+                kc.m = pm;
+                kc.n = pn;
+                kc.rg = kc.ra = (const int *)(intptr_t)(rows_off + pr0);
+                kc.cvoff = (const i64 *)(intptr_t)(cols_off + pc0);
+                kc.ct0 = kc.cg = kc.cb = (const int *)(intptr_t)(cols_off + pc0);
+                const bool pbig = pm >= SB_BM && pn >= BBN;
+                const int PBM = pbig ? SB_BM : SC_BM, PBN = pbig ? BBN : SC_BN;
+                for (int c = 0; !pbig && c < pn; ++c) fl_small += 2.0 * pm * (w - O.h_ct0[cols_off + pc0 + c]);
+                const int ptm = (pm + PBM - 1) / PBM, ptn = (pn + PBN - 1) / PBN;
+                // the part's own destination blocks (the parts' are disjoint)
+                KInfoHost ph;
+                const int a_lo = O.h_ra[rows_off + pr0], a_hi = O.h_ra[rows_off + pr0 + pm - 1];
+                const int b_lo = O.h_cb[cols_off + pc0], b_hi = O.h_cb[cols_off + pc0 + pn - 1];
+                for (int a = a_lo; a <= a_hi; ++a)
+                    for (int b = b_lo; b <= b_hi; ++b) ph.dests.push_back(kh.dests[(size_t)a * ujb.size() + b]);
+                // critical at this level / (far part) the twin's class at the next
+                vector<char> prow(ptm, 0), pcol(ptn, 0), trow(ptm, 0), tcol(ptn, 0);
+                for (int r = 0; r < pm; ++r) {
+                    const int lv = level_of[lib_[O.h_ra[rows_off + pr0 + r]]];
+                    if (lv == nl) prow[r / PBM] = 1;
+                    if (lv == nl + 1) trow[r / PBM] = 1;
+                }
+                for (int c = 0; c < pn; ++c) {
+                    const int lv = level_of[ujb[O.h_cb[cols_off + pc0 + c]]];
+                    if (lv == nl) pcol[c / PBN] = 1;
+                    if (lv == nl + 1) tcol[c / PBN] = 1;
+                }
+                const int slot = (int)O.kinfos.size();
+                O.kinfos.push_back(kc);
+                O.khost.push_back(std::move(ph));
+                if (pi == 2) {
+                    SLU_REQUIRE(pbig, "pair (%d, %d): far part of %d x %d", k, knext, pm, pn);
+                    O.far_slots.push_back({k, slot});
+                }
+                for (int i = 0; i < ptm; ++i)
+                    for (int j = 0; j < ptn; ++j) {
+                        if (pi == 2 && !(trow[i] || tcol[j])) { // deferred
+                            const int rows_t = std::min(PBM, pm - i * PBM), c1 = std::min(pn, (j + 1) * PBN);
+                            for (int cc = j * PBN; cc < c1; ++cc)
+                                fl_deferred += 2.0 * rows_t * (w - O.h_ct0[cols_off + pc0 + cc]);
+                            el_deferred += (double)rows_t * (c1 - j * PBN);
+                            continue;
+                        }
+                        const int cls = (prow[i] || pcol[j]) ? 0 : 1;
+                        (pbig ? O.big[cls][0] : O.small[cls][0]).push_back(TileItem{slot, i, j, slot});
+                        ++ntiles;
+                    }
+            }
+        }
+        for (int g = 0; knext < 0 && g < ng; ++g) {
             const int ga = g * gs, rows = std::min(gs, m - ga);
             KInfo<T> kg = ki;
             if (lcol_here) {
@@ -2232,19 +2434,32 @@ struct Plan : PlanBase {
                     for (int j = 0; j < tn; ++j) {
                         const int cls = (crow[i] || ccol[j]) ? 0 : 1;
                         const int ch = xmode ? std::max(g, j * BN / ucsz[k]) : 0;
-                        (big ? O.big[cls][ch] : O.small[cls][ch]).push_back(TileItem{slot0 + c, i, j});
+                        // second member of a pair: its rest tiles run the first
+                        // member's far tiles as their first K segment
+                        const bool fuse = kprev >= 0 && cls == 1;
+                        (big ? O.big[cls][ch] : O.small[cls][ch])
+                            .push_back(TileItem{slot0 + c, i, j, fuse ? SEG_PENDING + kprev : slot0 + c});
+                        if (fuse) {
+                            O.n_fused++;
+                            const int rows_t = std::min(BM, rows - i * BM);
+                            for (int cc = j * BN; cc < std::min(ncols, (j + 1) * BN); ++cc)
+                                fl_fused += 2.0 * rows_t * (W(kprev) - pt0[pt0.size() - ncols + cc]);
+                        }
                     }
         }
         // algorithmic work: exact unpadded flops and padded flops
         double fl = 0;
         for (int c = 0; c < ncols; ++c) fl += 2.0 * m * (w - O.h_ct0[cols_off + c]);
-        const double mult = cplx ? 4.0 : 1.0; // complex: 8 real flops per multiply-add
         O.schur_flops += fl * mult;
         O.schur_flops_padded += 2.0 * m * ncols * (double)(w - kmin) * mult;
-        O.scatter_bytes += 3.0 * sizeof(T) * (double)m * ncols;
-        O.n_schur_tiles += (i64)tm * tn;
-        O.R_schur_flops += fl * mult;
-        if (big) O.R_big_flops += fl * mult;
+        // (a deferred tile's scatter is its twin's)
+        O.scatter_bytes += 3.0 * sizeof(T) * ((double)m * ncols - el_deferred);
+        O.n_schur_tiles += ntiles;
+        // per level: an update counts where its tiles run, a pair's deferred
+        // tiles one level up with the second member
+        O.fused_flops += fl_fused * mult;
+        O.R_schur_flops += (fl - fl_deferred + fl_fused) * mult;
+        if (big) O.R_big_flops += (fl - fl_deferred + fl_fused - fl_small) * mult;
         if (w >= 64 && m >= 256 && ncols >= 256) O.R_big = true;
     }
 
@@ -2747,10 +2962,17 @@ struct Plan : PlanBase {
             path_counts[PC_DIAG_STRIPS]++;
         }
     }
-    void launch_big(const LevelRange &R, int off, int cnt, hipStream_t st) {
-        hipLaunchKernelGGL(k_schur_big<T>, dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
-                           d_tiles_big.p + off, d_kinfo.p + R.k_off, d_L.p, d_U.p,
-                           d_lblk.p, d_lmap.p, d_ublk.p, d_ucol_voff.p, d_ucol_fst.p);
+    // fused: the tiles of chained pairs that carry a first K segment (the
+    // last R.fused_n rest tiles of the level), through the two-segment instantiation
+    void launch_big(const LevelRange &R, int off, int cnt, hipStream_t st, bool fused = false) {
+        if (fused)
+            hipLaunchKernelGGL((k_schur_big<T, true>), dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
+                               d_tiles_big.p + off, d_kinfo.p + R.k_off, d_L.p, d_U.p,
+                               d_lblk.p, d_lmap.p, d_ublk.p, d_ucol_voff.p, d_ucol_fst.p);
+        else
+            hipLaunchKernelGGL((k_schur_big<T, false>), dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
+                               d_tiles_big.p + off, d_kinfo.p + R.k_off, d_L.p, d_U.p,
+                               d_lblk.p, d_lmap.p, d_ublk.p, d_ucol_voff.p, d_ucol_fst.p);
         path_counts[PC_SCHUR_BIG]++;
     }
     void launch_small(const LevelRange &R, int off, int cnt, hipStream_t st) {
@@ -2827,11 +3049,13 @@ struct Plan : PlanBase {
     // One Schur launch of n 128x128 tiles from off (its first n1, if any, as
     // a kernel launch of their own: one launch in the stats, two in
     // path_counts) / of n 64x64 tiles
-    void schur_big(const LevelRange &R, int off, int n_, hipStream_t st, int n1 = 0) {
+    // (its last nf tiles: fused ones, a launch of their own)
+    void schur_big(const LevelRange &R, int off, int n_, hipStream_t st, int n1 = 0, int nf = 0) {
         if (!n_) return;
         tm.span(2, st, [&] {
             if (n1 > 0) launch_big(R, off, n1, st);
-            if (n_ > n1) launch_big(R, off + n1, n_ - n1, st);
+            if (n_ - nf > n1) launch_big(R, off + n1, n_ - nf - n1, st);
+            if (nf > 0) launch_big(R, off + n_ - nf, nf, st, true);
         });
         stats.n_schur_launches++;
         stats.n_schur_big_launches++;
@@ -2920,8 +3144,8 @@ struct Plan : PlanBase {
         // the first rest_split %% of the big rest tiles as a launch of their own
         HIPCHK(hipStreamWaitEvent(stream, ev_pan[L], 0));
         const int nrest = R.big_n - R.bigc_n;
-        const int n1 = rest_split > 0 && !opts.serial ? (int)((i64)nrest * rest_split / 100) : 0;
-        schur_big(R, R.big_off + R.bigc_n, nrest, stream, n1);
+        const int n1 = rest_split > 0 && !opts.serial ? (int)((i64)(nrest - R.fused_n) * rest_split / 100) : 0;
+        schur_big(R, R.big_off + R.bigc_n, nrest, stream, n1, R.fused_n);
         schur_small(R, R.tile_off + R.tilec_n, R.tile_n - R.tilec_n, stream);
     }
 
@@ -3009,6 +3233,8 @@ struct Plan : PlanBase {
         stats.n_schur_big_launches = 0;
         std::fill(path_counts, path_counts + PC_N, 0);
         path_counts[PC_KSPLIT_KINFOS] = n_ksplit_kinfos;
+        path_counts[PC_SCHUR_PAIRS] = n_pairs;
+        path_counts[PC_SCHUR_FUSED_TILES] = n_fused_tiles;
         // 3D grids: my phases one after the other, each followed by its
         // ancestor reduction (SRC/pdgstrf3d.c:300-345)
         const int nph = zmode ? my_last + 1 : 1;

@@ -260,6 +260,11 @@ struct DRec {
 struct TileItem {
     int kslot; // index into the level's KInfo array
     int tm, tn;
+    // k_schur_big, fused tile of a chained supernode pair: the KInfo (index
+    // relative to the level's array; the previous level's lie below it) whose
+    // A / B operands run as a first K segment into the same accumulators;
+    // == kslot where the tile has one segment
+    int seg;
 };
 
 // destination tables
@@ -1258,7 +1263,10 @@ __device__ unsigned slu_stamp_n;
 #endif
 
 // 2 workgroups (16 waves) per CU need <= 128 VGPRs: ask for 4 waves per SIMD
-template <typename T>
+// FUSED: the instantiation for the fused tiles of chained supernode pairs
+// (TileItem::seg != kslot, two K segments); every other tile runs the plain
+// one, whose code and registers are those of the one-segment kernel.
+template <typename T, bool FUSED = false>
 __global__ void __launch_bounds__(BigCfg<T>::THREADS, BigCfg<T>::MINW)
 k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
             const LBlk *lblk, const int *lmap, const UBlk *ublk,
@@ -1338,13 +1346,31 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
     constexpr bool A16 = AE == 4 && std::is_same<T, double>::value;
     const int ar = A16 ? 2 * (tid & 63) : tid & (SB_BM - 1), ak = A16 ? tid >> 6 : tid / SB_BM;
     const bool avalid = ar < mrows;
-    const T *ap = ki.a + row0 + (A16 || avalid ? ar : 0);
     const int bc = tid / (SB_BK / BE), bk = (tid % (SB_BK / BE)) * BE;
     const bool bvalid = bc < ncols;
-    const int bcc = col0 + (bvalid ? bc : 0);
-    const int bt0 = ki.ct0[bcc];
-    const T *ub = ki.ubase + ki.cvoff[bcc] - bt0; // ub[t] valid for bt0 <= t < kmin + kw
-    const int tlast = ki.kmin + ki.kw - 1;
+    // The K segment under way: the operands of one supernode's update.  A
+    // fused tile (FUSED; ti.seg != ti.kslot) runs the far part of the pair's first
+    // member, then the second member's own update, into the same
+    // accumulators; both cover the tile's rows and columns from (row0, col0)
+    // of their KInfo.  The per-thread pointers are recomputed at the segment
+    // boundary rather than kept live (VGPR budget).
+    const T *ap, *ub; // ub[t] valid for bt0 <= t < kmin + kw
+    int bt0, kmin, kw, lda, tlast;
+    auto segment = [&](const KInfo<T> &k) {
+        kmin = k.kmin;
+        kw = k.kw;
+        lda = k.lda;
+        tlast = kmin + kw - 1;
+        // (fused: from an opaque copy of the thread index, so that the row and
+        // the column are recomputed here and not kept in registers across the K loop)
+        int t = tid;
+        if constexpr (FUSED) asm volatile("" : "+v"(t));
+        const int ar_ = A16 ? 2 * (t & 63) : t & (SB_BM - 1), bc_ = t / (SB_BK / BE);
+        const int bcc = col0 + (bc_ < ncols ? bc_ : 0);
+        ap = k.a + row0 + (A16 || ar_ < mrows ? ar_ : 0);
+        bt0 = k.ct0[bcc];
+        ub = k.ubase + k.cvoff[bcc] - bt0;
+    };
     // The zeroing of out-of-range elements happens at the LDS store, after
     // the current stage's MFMAs, so the prefetch's latency is not waited on
     // before them.
@@ -1354,24 +1380,24 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const int kk = k0 + ak + 8 * s;
-                gld2(ap + (int64_t)(ki.kmin + min(kk, ki.kw - 1)) * ki.lda, ra[2 * s], ra[2 * s + 1]);
+                gld2(ap + (int64_t)(kmin + min(kk, kw - 1)) * lda, ra[2 * s], ra[2 * s + 1]);
             }
         } else
 #pragma unroll
         for (int s = 0; s < AE; ++s) {
             const int kk = k0 + ak + (SB_THREADS / SB_BM) * s;
-            ra[s] = gld(ap + (int64_t)(ki.kmin + min(kk, ki.kw - 1)) * ki.lda);
+            ra[s] = gld(ap + (int64_t)(kmin + min(kk, kw - 1)) * lda);
         }
         // a column's 4 consecutive k through 16-byte loads, unclamped (the
         // buffers carry SB_UGUARD guards; 315.2 -> 310.7 ms at 100^3, Schur
         // 56.3 -> 57.0 %, and no spilled VGPRs, profiles/r03w_ab)
         if constexpr (BE == 4 && std::is_same<T, double>::value) { // (fp32: more spills)
-            gld4(ub + ki.kmin + k0 + bk, rb);
+            gld4(ub + kmin + k0 + bk, rb);
             return;
         }
 #pragma unroll
         for (int s = 0; s < BE; ++s) {
-            const int t = ki.kmin + k0 + bk + s;
+            const int t = kmin + k0 + bk + s;
             rb[s] = gld(ub + max(min(t, tlast), bt0));
         }
     };
@@ -1380,7 +1406,7 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
         if constexpr (A16) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const bool okk = k0 + ak + 8 * s < ki.kw;
+                const bool okk = k0 + ak + 8 * s < kw;
                 typedef double d2 __attribute__((ext_vector_type(2)));
                 *(d2 *)&sA[(ak + 8 * s) * LDS_A + ar] =
                     d2{keep_if(okk & (ar < mrows), ra[2 * s]), keep_if(okk & (ar + 1 < mrows), ra[2 * s + 1])};
@@ -1390,11 +1416,11 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
         for (int s = 0; s < AE; ++s) {
             const int kk = k0 + ak + (SB_THREADS / SB_BM) * s;
             sA[(ak + (SB_THREADS / SB_BM) * s) * LDS_A + ar] =
-                keep_if(avalid & (kk < ki.kw), ra[s]);
+                keep_if(avalid & (kk < kw), ra[s]);
         }
 #pragma unroll
         for (int s = 0; s < BE; ++s) {
-            const int t = ki.kmin + k0 + bk + s;
+            const int t = kmin + k0 + bk + s;
             sB[(bk + s) * LDS_B + bc] =
                 keep_if(bvalid & (t <= tlast) & (t >= bt0), rb[s]);
         }
@@ -1406,13 +1432,8 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
 #pragma unroll
         for (int b = 0; b < FN; ++b) acc[a][b] = M::zero();
 
-    const int nst = (ki.kw + SB_BK - 1) / SB_BK;
-    gload(0);
-    lstore(0, 0);
-    __syncthreads();
-    SB_STAMP(c1_);
-    auto mfma_stage = [&](int st) {
-        const T *sA = smem + (st & 1) * STAGE, *sB = sA + SB_BK * LDS_A;
+    auto mfma_stage = [&](int buf) {
+        const T *sA = smem + buf * STAGE, *sB = sA + SB_BK * LDS_A;
 #pragma unroll
         for (int ks = 0; ks < SB_BK; ks += M::KSTEP) {
             const int kl = ks + (lane >> 4);
@@ -1429,11 +1450,31 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
                 for (int fn = 0; fn < FN; ++fn) M::step(acc[fm][fn], av[fm], bv[fn]);
         }
     };
-    for (int st = 0; st + 1 < nst; ++st) {
-        gload((st + 1) * SB_BK);
-        mfma_stage(st);
-        lstore((st + 1) & 1, (st + 1) * SB_BK);
+    // The stage loop stays the only MFMA site besides the peeled last stage
+    // (a copy of the stage body at the segment boundary made the compiler
+    // move the accumulators through scratch).  A segment that is not the
+    // last runs all its stages in the loop: its last stage prefetches itself
+    // once more (unused), then the next segment starts from a drained
+    // pipeline; each segment pads its own K to SB_BK.
+    int buf = 0; // the LDS buffer that holds the current stage
+    for (int left = FUSED ? 1 : 0;; --left) {
+        segment(kinfo[left ? ti.seg : ti.kslot]);
+        gload(0);
+        lstore(buf, 0);
         __syncthreads();
+#ifdef SLU_SB_STAMP
+        if (left == (FUSED ? 1 : 0)) SB_STAMP(c1_); // the prologue ends with the first segment's first stage
+#endif
+        const int nst = (kw + SB_BK - 1) / SB_BK, nloop = nst - (left == 0);
+        for (int st = 0; st < nloop; ++st) {
+            const int k0 = min(st + 1, nst - 1) * SB_BK;
+            gload(k0);
+            mfma_stage(buf);
+            lstore(buf ^ 1, k0);
+            __syncthreads();
+            buf ^= 1;
+        }
+        if (left == 0) break;
     }
     // last stage (peeled: no prefetch, so its registers carry the second
     // half of the destination tables instead): per (row block, column) the
@@ -1467,7 +1508,7 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
             }
         }
     }
-    mfma_stage(nst - 1);
+    mfma_stage(buf);
     __syncthreads();
     if (tbl) {
         if (tid < CPN) s_cp[tid] = t_code ? t_code : (t_uv - t_fst) * 8;
@@ -1626,8 +1667,9 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
             o[0] = (t[rt_] & ((1ull << 40) - 1)) | (((wall_clock64() - t[rt_]) & 0xFFFFFFull) << 40);
             o[1] = (uint64_t)(t[c1_] - t[c0_]) | ((uint64_t)(t[c2_] - t[c1_]) << 32);
             o[2] = (uint64_t)(t[c3_] - t[c2_]) | ((uint64_t)hw << 32);
-            o[3] = (uint64_t)(xcc & 15) | ((uint64_t)ki.kw << 4) | ((uint64_t)mrows << 14) |
-                   ((uint64_t)ncols << 22) | ((uint64_t)ki.atomic << 30) | ((uint64_t)blockIdx.x << 32);
+            o[3] = (uint64_t)(xcc & 15) | ((uint64_t)kw << 4) | ((uint64_t)mrows << 14) |
+                   ((uint64_t)ncols << 22) | ((uint64_t)ki.atomic << 30) | ((uint64_t)FUSED << 31) |
+                   ((uint64_t)blockIdx.x << 32);
         }
     }
 #endif
