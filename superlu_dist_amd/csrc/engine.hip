@@ -82,6 +82,7 @@ struct LevelRange {
     double schur_flops = 0, big_flops = 0;
     int atomic_tiles = 0; // tiles of supernodes whose destinations collide within the level
     int fused_n = 0;      // big tiles that carry a deferred tile of the level below as a first K segment
+    int mapped_n = 0;     // the same of mapped pairs: the far part of the level below through a row map
     bool big = false;
     // 2D grids: the level's panel exchange in nch chunks (Plan::pchunks).
     // Chunk c = row group c of every L panel and column group c of every U
@@ -212,15 +213,15 @@ struct FactorTimer {
             stats.t_zreduce_ms += ms(zmarks[i][1], zmarks[i][2]);
         }
         if (timing >= 2) { // per-level breakdown (stderr)
-            fprintf(stderr, "[slu rank %d] lvl nsup diag trsm big small atomic  GFLOP  diag_ms trsm_ms big_ms small_ms comm_ms  TF/s wall_ms fused\n", iam);
+            fprintf(stderr, "[slu rank %d] lvl nsup diag trsm big small atomic  GFLOP  diag_ms trsm_ms big_ms small_ms comm_ms  TF/s wall_ms mapped fused\n", iam);
             for (size_t L = 0; L < levels.size(); ++L) {
                 const LevelRange &R = levels[L];
                 double sch = t[L][2] + t[L][3];
                 const float wall = ms(L ? lvl_end[L - 1] : e_start, lvl_end[L]);
-                fprintf(stderr, "[slu rank %d] %3zu %5zu %4d %5d %5d %5d %6d %7.2f %8.3f %7.3f %7.3f %7.3f %7.3f %6.2f %7.3f %5d\n",
+                fprintf(stderr, "[slu rank %d] %3zu %5zu %4d %5d %5d %5d %6d %7.2f %8.3f %7.3f %7.3f %7.3f %7.3f %6.2f %7.3f %5d %5d\n",
                         iam, L, bylev[L].size(), R.diag_n + R.df_n, R.lf_n + R.uf_n + R.tl_n + R.tu_n,
                         R.big_n, R.tile_n, R.atomic_tiles, R.schur_flops / 1e9, t[L][0], t[L][1], t[L][2], t[L][3],
-                        t[L][4], sch > 0 ? R.schur_flops / sch / 1e9 : 0.0, (double)wall, R.fused_n);
+                        t[L][4], sch > 0 ? R.schur_flops / sch / 1e9 : 0.0, (double)wall, R.mapped_n, R.fused_n);
             }
         }
         reset(0);
@@ -319,7 +320,8 @@ struct PlanBase {
         PC_DIAG_GENERIC, PC_DIAG_F, PC_DIAG_F_SMALL, PC_DIAG_WAVE32, PC_DIAG_WAVE64, PC_DIAG_STRIPS,
         PC_TRSM_REG64_PF, PC_TRSM_REG64_NOPF, PC_TRSM_REG128_PF, PC_TRSM_REG128_NOPF,
         PC_TRSM_REG256_PF, PC_TRSM_REG256_NOPF, PC_TRSM_BLK, PC_TRSM_GENERIC,
-        PC_SCHUR_BIG, PC_SCHUR_SMALL, PC_KSPLIT_KINFOS, PC_SCHUR_PAIRS, PC_SCHUR_FUSED_TILES, PC_N
+        PC_SCHUR_BIG, PC_SCHUR_SMALL, PC_KSPLIT_KINFOS, PC_SCHUR_PAIRS, PC_SCHUR_FUSED_TILES,
+        PC_SCHUR_MAP_PAIRS, PC_SCHUR_MAP_FUSED_TILES, PC_N
     };
     int64_t path_counts[PC_N] = {};
 };
@@ -622,6 +624,15 @@ struct Plan : PlanBase {
             for (auto &R : levels) bigf += R.big_flops;
             fprintf(stderr, "[slu plan %d]   (chained pairs %lld, fused tiles %lld, %.1f %% of the big-tile flops)\n", iam,
                     (long long)n_pairs, (long long)n_fused_tiles, bigf > 0 ? 100.0 * fused_flops / bigf : 0.0);
+        }
+        if (prof && n_map_pairs) {
+            double bigf = 0;
+            for (auto &R : levels) bigf += R.big_flops;
+            fprintf(stderr, "[slu plan %d]   (mapped pairs %lld, fused tiles %lld, %.3f GFLOP, %.1f %% of the big-tile flops; "
+                            "first-segment work on whole tiles %.1f %% above the far parts')\n", iam,
+                    (long long)n_map_pairs, (long long)n_map_fused_tiles, map_fused_flops / 1e9,
+                    bigf > 0 ? 100.0 * map_fused_flops / bigf : 0.0,
+                    map_useful > 0 ? 100.0 * (map_work / map_useful - 1.0) : 0.0);
         }
         tick("build_schedule");
         join_streams();
@@ -1723,6 +1734,8 @@ struct Plan : PlanBase {
         i64 n_ksplit = 0; // KInfo's of updates whose K range is split (SLU_KSPLIT_TILES)
         i64 n_fused = 0;  // tiles that carry a pair's first member as a first K segment
         double fused_flops = 0; // flops of those first segments
+        i64 n_mfused = 0;       // the same of mapped pairs (SLU_SCHUR_PAIR_MAP)
+        double mfused_flops = 0;
         vector<std::pair<int, int>> far_slots; // (first member of a pair, slot of its far KInfo)
         bool R_big = false;
     };
@@ -1746,6 +1759,32 @@ struct Plan : PlanBase {
     i64 n_pairs = 0, n_fused_tiles = 0;
     double fused_flops = 0; // flops that run as first segments of fused tiles
     static constexpr int SEG_PENDING = INT_MIN; // TileItem::seg = SEG_PENDING + k until the merge
+    // SLU_SCHUR_PAIR_MAP (default 1): among the supernodes the exact rule
+    // leaves free, k and its parent k' also pair where the far rows and
+    // columns of k are in-order subsequences of the rows and columns of k'
+    // (k' has rows of other subtrees besides).  A rest tile of k' that holds
+    // a row and a column of k runs the far part of k through a row map and
+    // mapped column tables as its first K segment (k_schur_big<T, 2>); the far
+    // elements of k in critical tile rows / columns of k' (one range of its
+    // far rows, one of its far columns, else no pair) run at k's own level as
+    // rectangles of their own.  A pair is formed only while the first
+    // segments' work on whole tiles of k' stays within 1 +
+    // SLU_SCHUR_PAIR_MAP_WASTE (default 0.05) of the far part's own.
+    // 0 plans the exact pairs only.
+    int schur_pair_map = env_int("SLU_SCHUR_PAIR_MAP", 1);
+    double pair_map_waste = [] {
+        const char *s = getenv("SLU_SCHUR_PAIR_MAP_WASTE");
+        return s && *s ? atof(s) : 0.05;
+    }();
+    struct MapPair {
+        vector<int> rmap, cmap;     // per row / column of k': index among the far rows / columns of k, or -1
+        int fm, fn;                 // far rows and columns of k
+        int r_lo, r_hi, c_lo, c_hi; // far rows / columns of k in critical tile rows / columns of k'
+    };
+    vector<MapPair> map_pairs;
+    vector<int> pair_map; // first members of mapped pairs: index into map_pairs, else -1
+    i64 n_map_pairs = 0, n_map_fused_tiles = 0;
+    double map_fused_flops = 0, map_work = 0, map_useful = 0;
 
     // rows of L(:,k) below the diagonal block: global index and block of each
     void sn_rows(int k, vector<int> &rg, vector<int> &rblk) const {
@@ -1786,6 +1825,7 @@ struct Plan : PlanBase {
         pair_next.assign(nsupers, -1);
         pair_prev.assign(nsupers, -1);
         far_kinfo.assign(nsupers, -1);
+        pair_map.assign(nsupers, -1);
         if (!schur_pair || xmode || zmode) return;
         constexpr int BBN = BigCfg<T>::BN;
         // (an update that SLU_KSPLIT_TILES may split is left alone)
@@ -1817,6 +1857,91 @@ struct Plan : PlanBase {
             pair_next[k] = kp;
             pair_prev[kp] = k;
             ++n_pairs;
+        }
+        if (!schur_pair_map) return;
+        // second pass: mapped pairs over the supernodes still free
+        for (int k = 0; k < nsupers; ++k) {
+            if (pair_prev[k] >= 0 || pair_next[k] >= 0 || !lidx[k] || !uidx[k] || may_split(k)) continue;
+            int m = 0, r0 = 0;
+            lrows(k, m, r0);
+            if (m < SB_BM) continue;
+            sn_rows(k, rg, rb);
+            sn_cols(k, cg, cb, t0);
+            const int n_ = (int)cg.size();
+            if (n_ < BBN) continue;
+            const int kp = rb[0];
+            if (cb[0] != kp || level_of[kp] != level_of[k] + 1 || pair_prev[kp] >= 0 || pair_next[kp] >= 0) continue;
+            if (!lidx[kp] || !uidx[kp] || may_split(kp)) continue;
+            int nr0 = 0, nc0 = 0;
+            while (nr0 < m && rb[nr0] == kp) ++nr0;
+            while (nc0 < n_ && cb[nc0] == kp) ++nc0;
+            const int fm = m - nr0, fn = n_ - nc0;
+            if (fm < SB_BM || fn < BBN) continue;
+            sn_rows(kp, rg2, rb2);
+            sn_cols(kp, cg2, cb2, t02);
+            MapPair mp;
+            mp.fm = fm;
+            mp.fn = fn;
+            // in-order subsequence: every far row (column) of k found, in order
+            auto submap = [](const vector<int> &sub, int s0, const vector<int> &all, vector<int> &map) {
+                map.assign(all.size(), -1);
+                size_t p = s0;
+                for (size_t q = 0; q < all.size() && p < sub.size(); ++q)
+                    if (all[q] == sub[p]) map[q] = (int)(p++ - s0);
+                return p == sub.size();
+            };
+            if (!submap(rg, nr0, rg2, mp.rmap) || !submap(cg, nc0, cg2, mp.cmap)) continue;
+            // tiles of k' : the rows and columns of k they hold; critical tile
+            // rows and columns of k' (a destination block one level above k')
+            const int m2 = (int)rg2.size(), n2 = (int)cg2.size();
+            const int tm2 = (m2 + SB_BM - 1) / SB_BM, tn2 = (n2 + BBN - 1) / BBN;
+            vector<int> rcnt(tm2, 0), ccnt(tn2, 0);
+            vector<char> crow(tm2, 0), ccol(tn2, 0);
+            for (int r = 0; r < m2; ++r) {
+                rcnt[r / SB_BM] += mp.rmap[r] >= 0;
+                if (level_of[rb2[r]] == level_of[kp] + 1) crow[r / SB_BM] = 1;
+            }
+            for (int c = 0; c < n2; ++c) {
+                ccnt[c / BBN] += mp.cmap[c] >= 0;
+                if (level_of[cb2[c]] == level_of[kp] + 1) ccol[c / BBN] = 1;
+            }
+            // the rows (columns) of k in critical tile rows (columns) of k': one range
+            auto crange = [](const vector<int> &map, const vector<char> &crit, int B, int &lo, int &hi) {
+                int cnt = 0;
+                lo = INT_MAX, hi = -1;
+                for (size_t q = 0; q < map.size(); ++q)
+                    if (map[q] >= 0 && crit[q / B]) {
+                        lo = std::min(lo, map[q]);
+                        hi = std::max(hi, map[q] + 1);
+                        ++cnt;
+                    }
+                if (!cnt) lo = hi = 0;
+                return cnt == hi - lo;
+            };
+            if (!crange(mp.rmap, crow, SB_BM, mp.r_lo, mp.r_hi) || !crange(mp.cmap, ccol, BBN, mp.c_lo, mp.c_hi)) continue;
+            // first-segment MFMA work on the tiles that hold a row and a column of k
+            double work = 0;
+            i64 el_fused = 0, nfused = 0;
+            for (int i = 0; i < tm2; ++i)
+                for (int j = 0; j < tn2; ++j) {
+                    if (!rcnt[i] || !ccnt[j]) continue;
+                    work += (double)std::min(SB_BM, m2 - i * SB_BM) * std::min(BBN, n2 - j * BBN);
+                    if (!crow[i] && !ccol[j]) {
+                        el_fused += (i64)rcnt[i] * ccnt[j];
+                        ++nfused;
+                    }
+                }
+            if (work > (1.0 + pair_map_waste) * fm * fn || !nfused) continue;
+            // every far element once: here by a part of k's own, or in one fused tile
+            SLU_REQUIRE(el_fused == (i64)(fm - (mp.r_hi - mp.r_lo)) * (fn - (mp.c_hi - mp.c_lo)),
+                        "mapped pair (%d, %d): %lld far elements in fused tiles", k, kp, (long long)el_fused);
+            pair_next[k] = kp;
+            pair_prev[kp] = k;
+            pair_map[k] = (int)map_pairs.size();
+            map_pairs.push_back(std::move(mp));
+            map_work += 2.0 * W(k) * work;
+            map_useful += 2.0 * W(k) * fm * fn;
+            ++n_map_pairs;
         }
     }
 
@@ -2002,6 +2127,9 @@ struct Plan : PlanBase {
                 n_fused_tiles += O.n_fused;
                 fused_flops += O.fused_flops;
                 R.fused_n += (int)O.n_fused;
+                n_map_fused_tiles += O.n_mfused;
+                map_fused_flops += O.mfused_flops;
+                R.mapped_n += (int)O.n_mfused;
                 R.schur_flops += O.R_schur_flops;
                 R.big_flops += O.R_big_flops;
                 R.big = R.big || O.R_big;
@@ -2046,15 +2174,20 @@ struct Plan : PlanBase {
                 if (cls == 0) {
                     R.bigc_n = bo[R.nch];
                     R.tilec_n = so[R.nch];
-                } else if (R.fused_n > 0) {
-                    // the fused tiles last among the rest tiles: they go out
-                    // as a launch of the two-segment kernel (one-process
+                } else if (R.fused_n + R.mapped_n > 0) {
+                    // the fused tiles last among the rest tiles, those of
+                    // mapped pairs after those of exact pairs: they go out
+                    // as launches of the two-segment kernels (one-process
                     // plans only: one chunk)
                     SLU_REQUIRE(!xmode && R.nch == 1, "level %d: fused tiles on a grid", L);
                     auto e = std::stable_partition(tiles_big.begin() + b0, tiles_big.end(),
                                                    [](const TileItem &x) { return x.seg == x.kslot; });
-                    SLU_REQUIRE(tiles_big.end() - e == R.fused_n, "level %d: %d fused tiles, %d counted", L,
-                                (int)(tiles_big.end() - e), R.fused_n);
+                    auto e2 = std::stable_partition(e, tiles_big.end(), [&](const TileItem &x) {
+                        return !kinfos[R.k_off + x.seg].mapped;
+                    });
+                    SLU_REQUIRE(e2 - e == R.fused_n && tiles_big.end() - e2 == R.mapped_n,
+                                "level %d: %d + %d fused tiles, %d + %d counted", L, (int)(e2 - e),
+                                (int)(tiles_big.end() - e2), R.fused_n, R.mapped_n);
                 }
             }
             R.big_n = (int)tiles_big.size() - R.big_off;
@@ -2326,6 +2459,16 @@ struct Plan : PlanBase {
         double fl_small = 0; // first member: flops of the parts that run 64x64 tiles
         i64 ntiles = (i64)tm * tn;
         if (kprev >= 0) sn_cols(kprev, pcg, pcb, pt0);
+        // second member of a mapped pair: rows / columns of the first per tile row / column
+        const MapPair *pmp = kprev >= 0 && pair_map[kprev] >= 0 ? &map_pairs[pair_map[kprev]] : nullptr;
+        vector<int> prc(pmp ? tm : 0, 0), pcc(pmp ? tn : 0, 0);
+        double fl_mfused = 0;
+        if (pmp) {
+            SLU_REQUIRE(big && (int)pmp->rmap.size() == m && (int)pmp->cmap.size() == ncols,
+                        "mapped pair (%d, %d): %d x %d", kprev, k, m, ncols);
+            for (int r = 0; r < m; ++r) prc[r / BM] += pmp->rmap[r] >= 0;
+            for (int c = 0; c < ncols; ++c) pcc[c / BN] += pmp->cmap[c] >= 0;
+        }
         if (knext >= 0) {
             // First member: the update in three parts, each a KInfo with a
             // tile grid of its own: near rows x all columns, far rows x near
@@ -2337,10 +2480,62 @@ struct Plan : PlanBase {
             int nr0 = 0, nc0 = 0;
             while (nr0 < m && lib_[O.h_ra[rows_off + nr0]] == knext) ++nr0;
             while (nc0 < ncols && ujb[O.h_cb[cols_off + nc0]] == knext) ++nc0;
-            const int part[3][4] = {{0, 0, nr0, ncols}, {nr0, 0, m - nr0, nc0}, {nr0, nc0, m - nr0, ncols - nc0}};
+            // (twin: the far part of an exact pair)
+            struct Part {
+                int r0, c0, m, n;
+                bool twin;
+            };
+            vector<Part> parts = {{0, 0, nr0, ncols, false}, {nr0, 0, m - nr0, nc0, false}};
+            const MapPair *mp = pair_map[k] >= 0 ? &map_pairs[pair_map[k]] : nullptr;
+            if (!mp) {
+                parts.push_back({nr0, nc0, m - nr0, ncols - nc0, true});
+            } else {
+                // Mapped pair: the far elements in critical tile rows of k'
+                // (far rows [r_lo, r_hi) x all far columns) and, of the other
+                // far rows, those in its critical tile columns run here; the
+                // rest is deferred to the fused tiles of k', which read it
+                // through a KInfo of its own: a = the far rows, rg = the row
+                // map, ct0 / cvoff per column of k' (an absent column: an
+                // empty segment, ct0 = w, at the first far column's values).
+                SLU_REQUIRE(mp->fm == m - nr0 && mp->fn == ncols - nc0, "mapped pair (%d, %d): far part", k, knext);
+                const int rl = mp->r_lo, rh = mp->r_hi, cl = mp->c_lo, ch = mp->c_hi;
+                parts.push_back({nr0 + rl, nc0, rh - rl, mp->fn, false});
+                parts.push_back({nr0, nc0 + cl, rl, ch - cl, false});
+                parts.push_back({nr0 + rh, nc0 + cl, mp->fm - rh, ch - cl, false});
+                for (int c = nc0; c < ncols; ++c) {
+                    if (c - nc0 >= cl && c - nc0 < ch) continue;
+                    fl_deferred += 2.0 * (mp->fm - (rh - rl)) * (w - O.h_ct0[cols_off + c]);
+                }
+                el_deferred = (double)(mp->fm - (rh - rl)) * (mp->fn - (ch - cl));
+                KInfo<T> ks = ki;
+                ks.a = d_L.p + lval_off[ljb] + r0 + nr0;
+                ks.lda = lval_ld[ljb];
+                ks.m = (int)mp->rmap.size();
+                ks.n = (int)mp->cmap.size();
+                ks.mapped = 1;
+                ks.rg = ks.ra = (const int *)(intptr_t)O.h_rg.size();
+                ks.cvoff = (const i64 *)(intptr_t)O.h_cg.size();
+                ks.ct0 = ks.cg = ks.cb = (const int *)(intptr_t)O.h_cg.size();
+                for (int q : mp->rmap) {
+                    O.h_rg.push_back(q);
+                    O.h_ra.push_back(0);
+                }
+                for (int q : mp->cmap) {
+                    O.h_cg.push_back(0);
+                    O.h_cb.push_back(0);
+                    const int t0q = q >= 0 ? O.h_ct0[cols_off + nc0 + q] : w;
+                    const i64 voq = O.h_cvoff[cols_off + nc0 + std::max(q, 0)];
+                    O.h_ct0.push_back(t0q);
+                    O.h_cvoff.push_back(voq);
+                }
+                O.far_slots.push_back({k, (int)O.kinfos.size()});
+                O.kinfos.push_back(ks);
+                O.khost.push_back(KInfoHost{}); // (no tile of its own at this level)
+            }
             ntiles = 0;
-            for (int pi = 0; pi < 3; ++pi) {
-                const int pr0 = part[pi][0], pc0 = part[pi][1], pm = part[pi][2], pn = part[pi][3];
+            for (size_t pi = 0; pi < parts.size(); ++pi) {
+                const int pr0 = parts[pi].r0, pc0 = parts[pi].c0, pm = parts[pi].m, pn = parts[pi].n;
+                const bool twin = parts[pi].twin;
                 if (pm <= 0 || pn <= 0) continue;
                 KInfo<T> kc = ki;
                 kc.a = d_L.p + lval_off[ljb] + r0 + pr0;
@@ -2375,13 +2570,13 @@ struct Plan : PlanBase {
                 const int slot = (int)O.kinfos.size();
                 O.kinfos.push_back(kc);
                 O.khost.push_back(std::move(ph));
-                if (pi == 2) {
+                if (twin) {
                     SLU_REQUIRE(pbig, "pair (%d, %d): far part of %d x %d", k, knext, pm, pn);
                     O.far_slots.push_back({k, slot});
                 }
                 for (int i = 0; i < ptm; ++i)
                     for (int j = 0; j < ptn; ++j) {
-                        if (pi == 2 && !(trow[i] || tcol[j])) { // deferred
+                        if (twin && !(trow[i] || tcol[j])) { // deferred
                             const int rows_t = std::min(PBM, pm - i * PBM), c1 = std::min(pn, (j + 1) * PBN);
                             for (int cc = j * PBN; cc < c1; ++cc)
                                 fl_deferred += 2.0 * rows_t * (w - O.h_ct0[cols_off + pc0 + cc]);
@@ -2436,14 +2631,20 @@ struct Plan : PlanBase {
                         const int ch = xmode ? std::max(g, j * BN / ucsz[k]) : 0;
                         // second member of a pair: its rest tiles run the first
                         // member's far tiles as their first K segment
-                        const bool fuse = kprev >= 0 && cls == 1;
+                        // (mapped pair: those that hold a row and a column of the first member)
+                        const bool fuse = kprev >= 0 && cls == 1 && (!pmp || (prc[i] && pcc[j]));
                         (big ? O.big[cls][ch] : O.small[cls][ch])
                             .push_back(TileItem{slot0 + c, i, j, fuse ? SEG_PENDING + kprev : slot0 + c});
-                        if (fuse) {
+                        if (fuse && !pmp) {
                             O.n_fused++;
                             const int rows_t = std::min(BM, rows - i * BM);
                             for (int cc = j * BN; cc < std::min(ncols, (j + 1) * BN); ++cc)
                                 fl_fused += 2.0 * rows_t * (W(kprev) - pt0[pt0.size() - ncols + cc]);
+                        } else if (fuse) {
+                            O.n_mfused++;
+                            for (int cc = j * BN; cc < std::min(ncols, (j + 1) * BN); ++cc)
+                                if (pmp->cmap[cc] >= 0)
+                                    fl_mfused += 2.0 * prc[i] * (W(kprev) - pt0[pt0.size() - pmp->fn + pmp->cmap[cc]]);
                         }
                     }
         }
@@ -2458,6 +2659,8 @@ struct Plan : PlanBase {
         // per level: an update counts where its tiles run, a pair's deferred
         // tiles one level up with the second member
         O.fused_flops += fl_fused * mult;
+        O.mfused_flops += fl_mfused * mult;
+        fl_fused += fl_mfused;
         O.R_schur_flops += (fl - fl_deferred + fl_fused) * mult;
         if (big) O.R_big_flops += (fl - fl_deferred + fl_fused - fl_small) * mult;
         if (w >= 64 && m >= 256 && ncols >= 256) O.R_big = true;
@@ -2964,13 +3167,18 @@ struct Plan : PlanBase {
     }
     // fused: the tiles of chained pairs that carry a first K segment (the
     // last R.fused_n rest tiles of the level), through the two-segment instantiation
-    void launch_big(const LevelRange &R, int off, int cnt, hipStream_t st, bool fused = false) {
-        if (fused)
-            hipLaunchKernelGGL((k_schur_big<T, true>), dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
+    // (fused = 2: those of mapped pairs, the last R.mapped_n, through the mapped instantiation)
+    void launch_big(const LevelRange &R, int off, int cnt, hipStream_t st, int fused = 0) {
+        if (fused == 2)
+            hipLaunchKernelGGL((k_schur_big<T, 2>), dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
+                               d_tiles_big.p + off, d_kinfo.p + R.k_off, d_L.p, d_U.p,
+                               d_lblk.p, d_lmap.p, d_ublk.p, d_ucol_voff.p, d_ucol_fst.p);
+        else if (fused)
+            hipLaunchKernelGGL((k_schur_big<T, 1>), dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
                                d_tiles_big.p + off, d_kinfo.p + R.k_off, d_L.p, d_U.p,
                                d_lblk.p, d_lmap.p, d_ublk.p, d_ucol_voff.p, d_ucol_fst.p);
         else
-            hipLaunchKernelGGL((k_schur_big<T, false>), dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
+            hipLaunchKernelGGL((k_schur_big<T, 0>), dim3(cnt), dim3(BigCfg<T>::THREADS), 0, st,
                                d_tiles_big.p + off, d_kinfo.p + R.k_off, d_L.p, d_U.p,
                                d_lblk.p, d_lmap.p, d_ublk.p, d_ucol_voff.p, d_ucol_fst.p);
         path_counts[PC_SCHUR_BIG]++;
@@ -3050,12 +3258,14 @@ struct Plan : PlanBase {
     // a kernel launch of their own: one launch in the stats, two in
     // path_counts) / of n 64x64 tiles
     // (its last nf tiles: fused ones, a launch of their own)
-    void schur_big(const LevelRange &R, int off, int n_, hipStream_t st, int n1 = 0, int nf = 0) {
+    // (and, after them, its last nm: fused tiles of mapped pairs, one more launch)
+    void schur_big(const LevelRange &R, int off, int n_, hipStream_t st, int n1 = 0, int nf = 0, int nm = 0) {
         if (!n_) return;
         tm.span(2, st, [&] {
             if (n1 > 0) launch_big(R, off, n1, st);
-            if (n_ - nf > n1) launch_big(R, off + n1, n_ - nf - n1, st);
-            if (nf > 0) launch_big(R, off + n_ - nf, nf, st, true);
+            if (n_ - nf - nm > n1) launch_big(R, off + n1, n_ - nf - nm - n1, st);
+            if (nf > 0) launch_big(R, off + n_ - nf - nm, nf, st, 1);
+            if (nm > 0) launch_big(R, off + n_ - nm, nm, st, 2);
         });
         stats.n_schur_launches++;
         stats.n_schur_big_launches++;
@@ -3144,8 +3354,9 @@ struct Plan : PlanBase {
         // the first rest_split %% of the big rest tiles as a launch of their own
         HIPCHK(hipStreamWaitEvent(stream, ev_pan[L], 0));
         const int nrest = R.big_n - R.bigc_n;
-        const int n1 = rest_split > 0 && !opts.serial ? (int)((i64)(nrest - R.fused_n) * rest_split / 100) : 0;
-        schur_big(R, R.big_off + R.bigc_n, nrest, stream, n1, R.fused_n);
+        const int nplain = nrest - R.fused_n - R.mapped_n;
+        const int n1 = rest_split > 0 && !opts.serial ? (int)((i64)nplain * rest_split / 100) : 0;
+        schur_big(R, R.big_off + R.bigc_n, nrest, stream, n1, R.fused_n, R.mapped_n);
         schur_small(R, R.tile_off + R.tilec_n, R.tile_n - R.tilec_n, stream);
     }
 
@@ -3235,6 +3446,8 @@ struct Plan : PlanBase {
         path_counts[PC_KSPLIT_KINFOS] = n_ksplit_kinfos;
         path_counts[PC_SCHUR_PAIRS] = n_pairs;
         path_counts[PC_SCHUR_FUSED_TILES] = n_fused_tiles;
+        path_counts[PC_SCHUR_MAP_PAIRS] = n_map_pairs;
+        path_counts[PC_SCHUR_MAP_FUSED_TILES] = n_map_fused_tiles;
         // 3D grids: my phases one after the other, each followed by its
         // ancestor reduction (SRC/pdgstrf3d.c:300-345)
         const int nph = zmode ? my_last + 1 : 1;

@@ -243,7 +243,11 @@ template <typename T> struct KInfo {
     const int *cb;       // per U column: index of its U block in the panel
     const int *pair;     // nLb x nUb destination handles
     const struct DRec *prec; // nLb x nUb destinations resolved at plan time
-    int lda, m, n, kmin, kw, nub, atomic, pad;
+    // mapped: the first K segment of a mapped pair's fused tiles (k_schur_big<T, 2>),
+    // indexed by the rows and columns of the pair's second member: rg = per
+    // row the row of `a` that holds it or -1, ct0 / cvoff = the column's
+    // segment (none: ct0 past the last k, cvoff of some column); no tiles of its own
+    int lda, m, n, kmin, kw, nub, atomic, mapped;
 };
 
 // One (L block ib, U block jb) destination of a panel, resolved by the plan
@@ -1266,7 +1270,12 @@ __device__ unsigned slu_stamp_n;
 // FUSED: the instantiation for the fused tiles of chained supernode pairs
 // (TileItem::seg != kslot, two K segments); every other tile runs the plain
 // one, whose code and registers are those of the one-segment kernel.
-template <typename T, bool FUSED = false>
+// FUSED = 2: the fused tiles of mapped pairs.  The tile's rows and columns
+// are the second member's; the first member has only some of them.  Its
+// segment's KInfo carries a row map (KInfo::mapped): a thread's A rows are
+// loaded one by one from the mapped rows (an absent row: row 0, zeroed at the
+// LDS store), and an absent column is an empty segment the B mask zeroes.
+template <typename T, int FUSED = 0>
 __global__ void __launch_bounds__(BigCfg<T>::THREADS, BigCfg<T>::MINW)
 k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
             const LBlk *lblk, const int *lmap, const UBlk *ublk,
@@ -1356,7 +1365,22 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
     // boundary rather than kept live (VGPR budget).
     const T *ap, *ub; // ub[t] valid for bt0 <= t < kmin + kw
     int bt0, kmin, kw, lda, tlast;
-    auto segment = [&](const KInfo<T> &k) {
+    // FUSED == 2: bit 0 (1): the thread's first (second, A16) row is present
+    // in the segment; from bit 2: the second row's distance from the first.
+    // fp64 has no register left for it (128 VGPRs, one spilled with it): the
+    // thread keeps it in an LDS word of its own and reads it back per stage.
+    constexpr bool APK_LDS = FUSED == 2 && A16;
+    __shared__ int s_apk[APK_LDS ? SB_THREADS : 1];
+    int apk = 0;
+    auto apk_get = [&]() -> int {
+        if constexpr (APK_LDS) return ((volatile int *)s_apk)[tid];
+        return apk;
+    };
+    auto apk_set = [&](int v) {
+        if constexpr (APK_LDS) ((volatile int *)s_apk)[tid] = v;
+        else apk = v;
+    };
+    auto segment = [&](const KInfo<T> &k, bool first) {
         kmin = k.kmin;
         kw = k.kw;
         lda = k.lda;
@@ -1367,7 +1391,19 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
         if constexpr (FUSED) asm volatile("" : "+v"(t));
         const int ar_ = A16 ? 2 * (t & 63) : t & (SB_BM - 1), bc_ = t / (SB_BK / BE);
         const int bcc = col0 + (bc_ < ncols ? bc_ : 0);
-        ap = k.a + row0 + (A16 || ar_ < mrows ? ar_ : 0);
+        if constexpr (FUSED == 2) {
+            if (first) { // through the row map
+                const int q0 = ar_ < mrows ? k.rg[row0 + ar_] : -1;
+                const int q1 = A16 && ar_ + 1 < mrows ? k.rg[row0 + ar_ + 1] : -1;
+                ap = k.a + max(q0, 0);
+                apk_set((max(q1, 0) - max(q0, 0)) * 4 + (q0 >= 0) + 2 * (q1 >= 0));
+            } else {
+                ap = k.a + row0 + (ar_ < mrows ? ar_ : 0);
+                apk_set((ar_ + 1 < mrows) * 6 + (ar_ < mrows));
+            }
+        } else {
+            ap = k.a + row0 + (A16 || ar_ < mrows ? ar_ : 0);
+        }
         bt0 = k.ct0[bcc];
         ub = k.ubase + k.cvoff[bcc] - bt0;
     };
@@ -1377,10 +1413,17 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
     T ra[AE], rb[BE];
     auto gload = [&](int k0) {
         if constexpr (A16) {
+            const int dl = FUSED == 2 ? apk_get() >> 2 : 0;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const int kk = k0 + ak + 8 * s;
-                gld2(ap + (int64_t)(kmin + min(kk, kw - 1)) * lda, ra[2 * s], ra[2 * s + 1]);
+                const T *p = ap + (int64_t)(kmin + min(kk, kw - 1)) * lda;
+                if constexpr (FUSED == 2) { // two rows that need not be neighbours
+                    ra[2 * s] = gld(p);
+                    ra[2 * s + 1] = gld(p + dl);
+                } else {
+                    gld2(p, ra[2 * s], ra[2 * s + 1]);
+                }
             }
         } else
 #pragma unroll
@@ -1404,19 +1447,22 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
     auto lstore = [&](int buf, int k0) {
         T *sA = smem + buf * STAGE, *sB = sA + SB_BK * LDS_A;
         if constexpr (A16) {
+            const int av = FUSED == 2 ? apk_get() : 0;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const bool okk = k0 + ak + 8 * s < kw;
                 typedef double d2 __attribute__((ext_vector_type(2)));
+                const bool ok0 = FUSED == 2 ? (av & 1) != 0 : ar < mrows;
+                const bool ok1 = FUSED == 2 ? (av & 2) != 0 : ar + 1 < mrows;
                 *(d2 *)&sA[(ak + 8 * s) * LDS_A + ar] =
-                    d2{keep_if(okk & (ar < mrows), ra[2 * s]), keep_if(okk & (ar + 1 < mrows), ra[2 * s + 1])};
+                    d2{keep_if(okk & ok0, ra[2 * s]), keep_if(okk & ok1, ra[2 * s + 1])};
             }
         } else
 #pragma unroll
         for (int s = 0; s < AE; ++s) {
             const int kk = k0 + ak + (SB_THREADS / SB_BM) * s;
             sA[(ak + (SB_THREADS / SB_BM) * s) * LDS_A + ar] =
-                keep_if(avalid & (kk < kw), ra[s]);
+                keep_if((FUSED == 2 ? (apk & 1) != 0 : avalid) & (kk < kw), ra[s]);
         }
 #pragma unroll
         for (int s = 0; s < BE; ++s) {
@@ -1458,7 +1504,7 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
     // pipeline; each segment pads its own K to SB_BK.
     int buf = 0; // the LDS buffer that holds the current stage
     for (int left = FUSED ? 1 : 0;; --left) {
-        segment(kinfo[left ? ti.seg : ti.kslot]);
+        segment(kinfo[left ? ti.seg : ti.kslot], left != 0);
         gload(0);
         lstore(buf, 0);
         __syncthreads();
@@ -1668,7 +1714,7 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
             o[1] = (uint64_t)(t[c1_] - t[c0_]) | ((uint64_t)(t[c2_] - t[c1_]) << 32);
             o[2] = (uint64_t)(t[c3_] - t[c2_]) | ((uint64_t)hw << 32);
             o[3] = (uint64_t)(xcc & 15) | ((uint64_t)kw << 4) | ((uint64_t)mrows << 14) |
-                   ((uint64_t)ncols << 22) | ((uint64_t)ki.atomic << 30) | ((uint64_t)FUSED << 31) |
+                   ((uint64_t)ncols << 22) | ((uint64_t)ki.atomic << 30) | ((uint64_t)(FUSED != 0) << 31) |
                    ((uint64_t)blockIdx.x << 32);
         }
     }

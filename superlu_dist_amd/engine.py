@@ -315,13 +315,15 @@ class Plan:
                  "diag_strips", "trsm_reg64_pf", "trsm_reg64_nopf", "trsm_reg128_pf",
                  "trsm_reg128_nopf", "trsm_reg256_pf", "trsm_reg256_nopf", "trsm_blk",
                  "trsm_generic", "schur_big", "schur_small", "ksplit_kinfos", "schur_pairs",
-                 "schur_fused_tiles")
+                 "schur_fused_tiles", "schur_map_pairs", "schur_map_fused_tiles")
 
     def path_counts(self):
         """Kernel launches of the last factor() by dispatch path
         (slu_plan_path_counts; ksplit_kinfos counts the KInfo's of K-split
         Schur updates instead, schur_pairs the plan's chained supernode pairs
-        and schur_fused_tiles the tile pairs they run as one, SLU_SCHUR_PAIR)."""
+        and schur_fused_tiles the tile pairs they run as one, SLU_SCHUR_PAIR;
+        schur_map_pairs / schur_map_fused_tiles the same of the pairs whose
+        second member has rows and columns of its own, SLU_SCHUR_PAIR_MAP)."""
         out = np.zeros(len(self.PATH_KEYS), dtype=np.int64)
         n = lib().slu_plan_path_counts(self.ptr, as_i64p(out), len(out))
         if n != len(out):
