@@ -296,6 +296,22 @@ int slu_plan_refine_t(slu_plan *p, int trans, const void *b, void *x, int64_t ld
  * rcond_info: sweeps and device time (ms) of the last slu_plan_rcond. */
 int slu_plan_rcond(slu_plan *p, int norm /* '1' or 'I' */, double anorm, double *rcond);
 int slu_plan_rcond_info(const slu_plan *p, int *sweeps, double *ms);
+/* L U X = B for nrhs columns at once on the device factors (1x1 plans; 2D
+ * and 3D plans refused), SVB_NR columns per pass over the factors (32 in
+ * fp64 and fp32, 16 in complex), the panel products on MFMA
+ * (csrc/solve_block.h).  b: column-major, ld ldb >= n, element type of the
+ * plan, overwritten with X; on_device = 0: host array; 1: device pointer
+ * (the caller's writes must have completed; the call returns after the
+ * device finished).  Columns >= nrhs and rows >= n of b are not touched.
+ * The working copy of X (n rows of SVB_NR values, row-major) is a device
+ * buffer of the plan, allocated at the first call and kept; a host b goes
+ * through a second buffer of that size.  Nothing dispatches here
+ * automatically: below one pass's worth of columns slu_plan_solve is the
+ * faster call.  t_solve_ms in the stats is the device time of the last call
+ * (on_device = 0: without the PCIe copies). */
+int slu_plan_solve_block(slu_plan *p, void *b, int64_t ldb, int nrhs, int on_device);
+/* passes over the factors, kernel launches and device ms of the last call */
+int slu_plan_solve_block_info(const slu_plan *p, int *passes, int64_t *launches, double *ms);
 /* Schedule-only plans: replay every level's exchange phases of
  * slu_plan_factor through the communicator on host buffers; each received
  * section is checked byte for byte against what its root wrote.  Collective;
@@ -327,7 +343,7 @@ typedef struct {
     int64_t n_schur_big_launches;
     double comm_bytes;         /* bytes of the broadcast sections this rank
                                   takes part in (as root or receiver) per factor */
-    double t_solve_ms;         /* device time of the last slu_plan_solve / solve_t */
+    double t_solve_ms;         /* device time of the last slu_plan_solve / solve_t / solve_block */
     double t_fill_ms;          /* device time of the last slu_plan_fill_a */
     double t_refine_ms;        /* device time of the last slu_plan_refine / refine_t */
     /* host wall times of the drop-in path (ms) */

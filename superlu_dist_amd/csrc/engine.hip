@@ -48,6 +48,7 @@
 #include "diag_wave.h"
 #include "fill.h"
 #include "solve.h"
+#include "solve_block.h"
 #include "refine_d2.h"
 #include "hostio.h"
 #include "amalg.h"
@@ -294,6 +295,12 @@ struct PlanBase {
     virtual void sync() = 0;
     virtual void set_timing(int timing, int serial) = 0;
     virtual void solve(void *b, int64_t ldb, int nrhs) = 0;
+    // L U X = B, SvbNr columns per pass over the factors on MFMA (1x1 plans;
+    // solve_block.h); passes, launches and device time of the call in svb_*
+    virtual void solve_block(void *b, int64_t ldb, int nrhs, int on_device) = 0;
+    int svb_passes = 0;
+    int64_t svb_launches = 0;
+    double svb_ms = 0;
     virtual void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) = 0;
     virtual void fill_a(const void *a, int on_device) = 0;
     virtual void refine(const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) = 0;
@@ -3930,6 +3937,90 @@ struct Plan : PlanBase {
         stats.t_solve_ms = total;
     }
 
+    // ---- block solve (solve_block.h): SvbNr right-hand sides per pass over
+    // the factors, in a row-major working buffer allocated on first use
+    DevBuf<T> d_svb_x, d_svb_stage;
+    // the level order of sweep_nr on the row-major X; returns the launches
+    i64 sweep_block(T *xb) {
+        const int nl = (int)bylev.size();
+        i64 nk = 0;
+        for (int L = 0; L < nl; ++L) { // L Y = B
+            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_l_off[L + 1] - sv_l_off[L];
+            if (nd)
+                hipLaunchKernelGGL((k_svb_ldiag<T>), dim3(nd), dim3(SVB_DTHREADS), 0, stream,
+                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xb);
+            if (nc)
+                hipLaunchKernelGGL((k_svb_lpanel<T>), dim3(nc), dim3(SVB_LTHREADS), 0, stream,
+                                   d_sv_lch.p + sv_l_off[L], d_sv_pan.p, d_sv_roff.p,
+                                   d_sv_rows.p, d_L.p, xb);
+            nk += (nd > 0) + (nc > 0);
+        }
+        for (int L = nl - 1; L >= 0; --L) { // U X = Y
+            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_u_off[L + 1] - sv_u_off[L];
+            if (nc)
+                hipLaunchKernelGGL((k_svb_upanel<T>), dim3(nc), dim3(SV_THREADS), 0, stream,
+                                   d_sv_uch.p + sv_u_off[L], d_sv_diag.p, d_sv_coff.p,
+                                   d_sv_ncol.p, d_ucol_voff.p, d_ucol_fst.p, d_sv_gc.p,
+                                   d_U.p, xb);
+            if (nd)
+                hipLaunchKernelGGL((k_svb_udiag<T>), dim3(nd), dim3(SVB_DTHREADS), 0, stream,
+                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xb);
+            nk += (nd > 0) + (nc > 0);
+        }
+        HIPCHK(hipGetLastError());
+        return nk;
+    }
+    void solve_block(void *b, int64_t ldb, int nrhs, int on_device) override {
+        SLU_REQUIRE(!zmode, "solve_block: not on 3D plans (the block sweep runs on 1x1 plans only)");
+        SLU_REQUIRE(!xmode, "solve_block: not on a %dx%d grid (the block sweep has no exchanges; "
+                    "1x1 plans only)", Pr, Pc);
+        SLU_REQUIRE(vstate == 2, "solve_block: the device storage holds no factors (factor first)");
+        SLU_REQUIRE(ldb >= n && nrhs >= 0, "solve_block: ldb %lld < n %d or nrhs %d < 0", (long long)ldb, n, nrhs);
+        svb_passes = 0;
+        svb_launches = 0;
+        svb_ms = 0;
+        stats.t_solve_ms = 0;
+        if (nrhs == 0 || n == 0) return;
+        if (!sv_ready) build_solve();
+        constexpr int NRB = SvbNr<T>::v;
+        const size_t nn = (size_t)n;
+        if (d_svb_x.n < nn * NRB) d_svb_x.alloc(nn * NRB);
+        if (!on_device && d_svb_stage.n < nn * NRB) d_svb_stage.alloc(nn * NRB);
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        const unsigned tb = (unsigned)((n + SVB_TR_ROWS - 1) / SVB_TR_ROWS);
+        float total = 0;
+        for (int r0 = 0; r0 < nrhs; r0 += NRB) {
+            const int nr = std::min(NRB, nrhs - r0);
+            T *cols = on_device ? (T *)b + (i64)r0 * ldb : d_svb_stage.p; // the pass's columns on the device
+            const i64 ldc = on_device ? ldb : (i64)n;
+            if (!on_device)
+                for (int q = 0; q < nr; ++q)
+                    HIPCHK(hipMemcpyAsync(cols + (i64)q * n, (HT *)b + (i64)(r0 + q) * ldb,
+                                          nn * sizeof(T), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipEventRecord(e0, stream));
+            hipLaunchKernelGGL((k_svb_in<T>), dim3(tb), dim3(256), 0, stream, (const T *)cols, ldc, n, nr, d_svb_x.p);
+            svb_launches += 2 + sweep_block(d_svb_x.p);
+            hipLaunchKernelGGL((k_svb_out<T>), dim3(tb), dim3(256), 0, stream, (const T *)d_svb_x.p, n, nr, cols, ldc);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(e1, stream));
+            if (!on_device)
+                for (int q = 0; q < nr; ++q)
+                    HIPCHK(hipMemcpyAsync((HT *)b + (i64)(r0 + q) * ldb, cols + (i64)q * n,
+                                          nn * sizeof(T), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            float ms = 0;
+            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+            total += ms;
+            ++svb_passes;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        svb_ms = total;
+        stats.t_solve_ms = total;
+    }
+
     // Iterative refinement on the device (SRC/pdgsrfs.c:197-253, 1x1 grid,
     // permuted coordinates): R = B - A X and S = |A||X| + |B| by rows of A
     // (k_resid), componentwise backward error berr = max |R_i| / S_i with the
@@ -4784,6 +4875,19 @@ int slu_plan_solve(slu_plan *p, void *b, int64_t ldb, int nrhs) {
     return guarded([&] {
         p->impl->solve(b, ldb, nrhs);
     });
+}
+
+int slu_plan_solve_block(slu_plan *p, void *b, int64_t ldb, int nrhs, int on_device) {
+    return guarded([&] {
+        p->impl->solve_block(b, ldb, nrhs, on_device);
+    });
+}
+
+int slu_plan_solve_block_info(const slu_plan *p, int *passes, int64_t *launches, double *ms) {
+    if (passes) *passes = p->impl->svb_passes;
+    if (launches) *launches = p->impl->svb_launches;
+    if (ms) *ms = p->impl->svb_ms;
+    return 0;
 }
 
 int slu_plan_set_a_pattern(slu_plan *p, int64_t ncol, const int64_t *xa, const int64_t *asub) {

@@ -85,6 +85,13 @@ struct CoarsePlan : PlanBase {
         in->solve(b, ldb, nrhs);
         sync_stats();
     }
+    void solve_block(void *b, int64_t ldb, int nrhs, int on_device) override {
+        in->solve_block(b, ldb, nrhs, on_device);
+        svb_passes = in->svb_passes;
+        svb_launches = in->svb_launches;
+        svb_ms = in->svb_ms;
+        sync_stats();
+    }
     void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) override {
         in->set_a_pattern(ncol, xa, asub);
         sync_stats();

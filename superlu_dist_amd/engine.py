@@ -215,6 +215,31 @@ class Plan:
                                              x.ctypes.data_as(C.c_void_p), n, nrhs))
         return x
 
+    def solve_block(self, b):
+        """Solve L U X = B for a block of right-hand sides: every factor
+        element is read once per sweep for 32 columns (16 complex), the panel
+        products on MFMA (1x1 plans).  b: (n,) or (n, nrhs).  Returns x as
+        solve() does; the caller chooses between the two (solve() is the
+        faster one for a few columns)."""
+        dt = self.lu.Lval.dtype
+        x = np.array(b, dtype=dt, order="F", copy=True)
+        nrhs = 1 if x.ndim == 1 else x.shape[1]
+        self._chk(lib().slu_plan_solve_block(self.ptr, x.ctypes.data_as(C.c_void_p),
+                                             x.shape[0], nrhs, 0))
+        return x
+
+    def solve_block_dev(self, ptr, ldb, nrhs):
+        """solve_block in place on a column-major device array (raw pointer,
+        leading dimension ldb >= n, the plan's element type); returns after
+        the device finished."""
+        self._chk(lib().slu_plan_solve_block(self.ptr, C.c_void_p(int(ptr)), int(ldb), int(nrhs), 1))
+
+    def solve_block_info(self):
+        """(passes over the factors, kernel launches, device ms) of the last solve_block."""
+        k, nl, ms = C.c_int(), C.c_int64(), C.c_double()
+        lib().slu_plan_solve_block_info(self.ptr, C.byref(k), C.byref(nl), C.byref(ms))
+        return k.value, nl.value, ms.value
+
     def set_a_pattern(self, colptr, rowind):
         """Pattern of A in the LUstruct's permuted coordinates (CSC)."""
         self._xa = np.ascontiguousarray(colptr, dtype=np.int64)

@@ -177,6 +177,8 @@ def lib():
                                         C.POINTER(C.c_double), c_intp]),
         "slu_plan_rcond": (C.c_int, [P, C.c_int, C.c_double, C.POINTER(C.c_double)]),
         "slu_plan_rcond_info": (C.c_int, [P, c_intp, C.POINTER(C.c_double)]),
+        "slu_plan_solve_block": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_int]),
+        "slu_plan_solve_block_info": (C.c_int, [P, c_intp, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
         "slu_plan_fill_a_d2": (C.c_int, [P, P, C.c_int]),
         "slu_plan_refine_d2": (C.c_int, [P, P, P, C.c_int64, C.c_int, C.POINTER(C.c_double),
                                          c_intp]),
