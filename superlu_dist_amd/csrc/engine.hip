@@ -229,6 +229,33 @@ struct FactorTimer {
     }
 };
 
+// Device time of a stretch of one stream's work: two events that live as long
+// as the object, whichever way its scope is left.  start / stop only record;
+// ms() waits for the second event.
+struct EventTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventTimer() {
+        HIPCHK(hipEventCreate(&e0));
+        const hipError_t err = hipEventCreate(&e1);
+        if (err != hipSuccess) (void)hipEventDestroy(e0); // no destructor after a throwing constructor
+        HIPCHK(err);
+    }
+    EventTimer(const EventTimer &) = delete;
+    EventTimer &operator=(const EventTimer &) = delete;
+    ~EventTimer() {
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    void start(hipStream_t st) { HIPCHK(hipEventRecord(e0, st)); }
+    void stop(hipStream_t st) { HIPCHK(hipEventRecord(e1, st)); }
+    float ms() {
+        float t = 0;
+        HIPCHK(hipEventSynchronize(e1));
+        HIPCHK(hipEventElapsedTime(&t, e0, e1));
+        return t;
+    }
+};
+
 // Slot of the overlapped D2H's pinned-slot pipeline (Plan::run_d2h);
 // SLU_D2H_SLOT_KB overrides it: tests use tiny slots so that blocks split
 // across fills.
@@ -3525,7 +3552,7 @@ struct Plan : PlanBase {
     }
 
     // ------------------------------------------------------- device solve
-    // (1x1; solve.h).  Tables are built on the first call and kept.
+    // (solve.h).  Tables are built on the first call (build_solve) and kept.
     bool sv_ready = false;
     vector<int> sv_d_off, sv_l_off, sv_u_off; // per level: diag items, L chunks, U chunks
     DevBuf<SvDiag> d_sv_diag, d_sv_lvl;       // per supernode / in level order
@@ -3535,100 +3562,41 @@ struct Plan : PlanBase {
     DevBuf<int> d_sv_rows, d_sv_ncol, d_sv_gc;
     DevBuf<T> d_sv_x;
 
-    void build_solve() {
-        if (xmode) return build_solve_2d();
-        vector<SvDiag> dg(nsupers), lvl;
-        vector<i64> roff(nsupers), coff(nsupers, 0);
-        vector<int> rows, ncol(nsupers, 0), gc;
-        for (int k = 0; k < nsupers; ++k) {
-            SLU_REQUIRE(lval_off[k] >= 0, "supernode %d has no L column block", k);
-            SvDiag d{};
-            d.voff = lval_off[k];
-            d.ld = lval_ld[k];
-            d.w = W(k);
-            d.fst = (int)xsup[k];
-            dg[k] = d;
-            roff[k] = (i64)rows.size();
-            const int_t *ix = lidx[k];
-            i64 p = SLU_BC_HEADER;
-            for (i64 b = 0; b < ix[0]; ++b) {
-                const int gb = (int)ix[p], nr = (int)ix[p + 1];
-                if (gb != k)
-                    for (int i = 0; i < nr; ++i) rows.push_back((int)ix[p + 2 + i]);
-                p += SLU_LB_DESCRIPTOR + nr;
-            }
-            SLU_REQUIRE((i64)rows.size() - roff[k] == d.ld - d.w, "supernode %d: panel rows", k);
-            if (uval_off[k] >= 0 && urow_nblk[k] > 0) {
-                coff[k] = ublk[urow_first[k]].coloff;
-                for (int b = urow_first[k]; b < urow_first[k] + urow_nblk[k]; ++b) ncol[k] += W(ublk_jb[b]);
-            }
-        }
-        gc.resize(ucol_voff.size());
-        for (size_t b = 0; b < ublk.size(); ++b)
-            for (int c = 0; c < W(ublk_jb[b]); ++c) gc[ublk[b].coloff + c] = ublk[b].fcol + c;
-        vector<SvChunk> lch, uch;
-        const int nl = (int)bylev.size();
-        sv_d_off.assign(nl + 1, 0);
-        sv_l_off.assign(nl + 1, 0);
-        sv_u_off.assign(nl + 1, 0);
-        for (int L = 0; L < nl; ++L) {
-            sv_d_off[L] = (int)lvl.size();
-            sv_l_off[L] = (int)lch.size();
-            sv_u_off[L] = (int)uch.size();
-            for (int k : bylev[L]) {
-                lvl.push_back(dg[k]);
-                for (int r0 = 0; r0 < dg[k].ld - dg[k].w; r0 += SV_THREADS) lch.push_back({k, r0});
-                for (int c0 = 0; c0 < ncol[k]; c0 += SVU_COLS) uch.push_back({k, c0});
-            }
-        }
-        sv_d_off[nl] = (int)lvl.size();
-        sv_l_off[nl] = (int)lch.size();
-        sv_u_off[nl] = (int)uch.size();
-        d_sv_diag.upload(dg);
-        {
-            vector<SvDiag> pan(dg);
-            for (auto &d : pan) {
-                d.pad = d.ld - d.w;
-                d.voff += d.w;
-            }
-            d_sv_pan.upload(pan);
-        }
-        d_sv_lvl.upload(lvl);
-        d_sv_lch.upload(lch);
-        d_sv_uch.upload(uch);
-        d_sv_roff.upload(roff);
-        d_sv_coff.upload(coff);
-        d_sv_rows.upload(rows.empty() ? vector<int>(1, 0) : rows);
-        d_sv_ncol.upload(ncol);
-        d_sv_gc.upload(gc.empty() ? vector<int>(1, 0) : gc);
-        d_sv_x.alloc(std::max(n, 1));
-        HIPCHK(hipDeviceSynchronize()); // pageable table uploads landed (non-blocking streams)
-        sv_ready = true;
+    // One kernel over level L's diagonal items, L chunks or U chunks on
+    // `stream`: the table arguments every kernel of that family starts with,
+    // then `tail`.  Nothing is launched for an empty level; returns whether
+    // it launched.
+    template <typename K, typename... A> bool sv_diag(int L, K kernel, unsigned threads, A... tail) {
+        const int nd = sv_d_off[L + 1] - sv_d_off[L];
+        if (nd)
+            hipLaunchKernelGGL(kernel, dim3(nd), dim3(threads), 0, stream, d_sv_lvl.p + sv_d_off[L], d_L.p, tail...);
+        return nd > 0;
+    }
+    template <typename K, typename... A> bool sv_lpan(int L, K kernel, unsigned threads, A... tail) {
+        const int nc = sv_l_off[L + 1] - sv_l_off[L];
+        if (nc)
+            hipLaunchKernelGGL(kernel, dim3(nc), dim3(threads), 0, stream, d_sv_lch.p + sv_l_off[L], d_sv_pan.p,
+                               d_sv_roff.p, d_sv_rows.p, d_L.p, tail...);
+        return nc > 0;
+    }
+    template <typename K, typename... A> bool sv_upan(int L, K kernel, unsigned threads, A... tail) {
+        const int nc = sv_u_off[L + 1] - sv_u_off[L];
+        if (nc)
+            hipLaunchKernelGGL(kernel, dim3(nc), dim3(threads), 0, stream, d_sv_uch.p + sv_u_off[L], d_sv_diag.p,
+                               d_sv_coff.p, d_sv_ncol.p, d_ucol_voff.p, d_ucol_fst.p, d_sv_gc.p, d_U.p, tail...);
+        return nc > 0;
     }
 
     // L and U sweeps over nr <= SV_NR device vectors xv (ld ldx, in place), on `stream`
     template <int NR> void sweep_nr(T *xv, i64 ldx, int nr) {
         const int nl = (int)bylev.size();
         for (int L = 0; L < nl; ++L) { // L y = b
-            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_l_off[L + 1] - sv_l_off[L];
-            if (nd)
-                hipLaunchKernelGGL((k_sv_ldiag<T, NR>), dim3(nd), dim3(SVD_THREADS), 0, stream,
-                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xv, ldx, nr);
-            if (nc)
-                hipLaunchKernelGGL((k_sv_lpanel<T, NR>), dim3(nc), dim3(SV_THREADS), 0, stream,
-                                   d_sv_lch.p + sv_l_off[L], d_sv_pan.p, d_sv_roff.p,
-                                   d_sv_rows.p, d_L.p, xv, ldx, nr);
+            sv_diag(L, k_sv_ldiag<T, NR>, SVD_THREADS, xv, ldx, nr);
+            sv_lpan(L, k_sv_lpanel<T, NR>, SV_THREADS, xv, ldx, nr);
         }
         for (int L = nl - 1; L >= 0; --L) { // U x = y
-            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_u_off[L + 1] - sv_u_off[L];
-            if (nc)
-                hipLaunchKernelGGL((k_sv_upanel<T, NR>), dim3(nc), dim3(SV_THREADS), 0, stream,
-                                   d_sv_uch.p + sv_u_off[L], d_sv_diag.p, d_sv_coff.p,
-                                   d_sv_ncol.p, d_ucol_voff.p, d_ucol_fst.p, d_sv_gc.p,
-                                   d_U.p, xv, ldx, nr);
-            if (nd)
-                hipLaunchKernelGGL((k_sv_udiag<T, NR>), dim3(nd), dim3(SVD_THREADS), 0, stream,
-                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xv, ldx, nr);
+            sv_upan(L, k_sv_upanel<T, NR>, SV_THREADS, xv, ldx, nr);
+            sv_diag(L, k_sv_udiag<T, NR>, SVD_THREADS, xv, ldx, nr);
         }
         HIPCHK(hipGetLastError());
     }
@@ -3642,25 +3610,12 @@ struct Plan : PlanBase {
     template <int NR> void sweep_t_nr(T *xv, i64 ldx, int nr, int conj) {
         const int nl = (int)bylev.size();
         for (int L = 0; L < nl; ++L) {
-            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_u_off[L + 1] - sv_u_off[L];
-            if (nd)
-                hipLaunchKernelGGL((k_sv_utdiag<T, NR>), dim3(nd), dim3(SVD_THREADS), 0, stream,
-                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xv, ldx, nr, conj);
-            if (nc)
-                hipLaunchKernelGGL((k_sv_utpanel<T, NR>), dim3(nc), dim3(SV_THREADS), 0, stream,
-                                   d_sv_uch.p + sv_u_off[L], d_sv_diag.p, d_sv_coff.p,
-                                   d_sv_ncol.p, d_ucol_voff.p, d_ucol_fst.p, d_sv_gc.p,
-                                   d_U.p, xv, ldx, nr, conj);
+            sv_diag(L, k_sv_utdiag<T, NR>, SVD_THREADS, xv, ldx, nr, conj);
+            sv_upan(L, k_sv_utpanel<T, NR>, SV_THREADS, xv, ldx, nr, conj);
         }
         for (int L = nl - 1; L >= 0; --L) {
-            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_l_off[L + 1] - sv_l_off[L];
-            if (nc)
-                hipLaunchKernelGGL((k_sv_ltpanel<T, NR>), dim3(nc), dim3(SV_THREADS), 0, stream,
-                                   d_sv_lch.p + sv_l_off[L], d_sv_pan.p, d_sv_roff.p,
-                                   d_sv_rows.p, d_L.p, xv, ldx, nr, conj);
-            if (nd)
-                hipLaunchKernelGGL((k_sv_ltdiag<T, NR>), dim3(nd), dim3(SVD_THREADS), 0, stream,
-                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xv, ldx, nr, conj);
+            sv_lpan(L, k_sv_ltpanel<T, NR>, SV_THREADS, xv, ldx, nr, conj);
+            sv_diag(L, k_sv_ltdiag<T, NR>, SVD_THREADS, xv, ldx, nr, conj);
         }
         HIPCHK(hipGetLastError());
     }
@@ -3679,6 +3634,13 @@ struct Plan : PlanBase {
         SLU_REQUIRE(!xmode, "%s: not on a %dx%d grid (the transposed sweep swaps the roles of process "
                     "rows and columns; 1x1 plans only)", what, Pr, Pc);
         SLU_REQUIRE(vstate == 2, "%s: the device storage holds no factors (factor first)", what);
+    }
+    // the same rules in solve_block's words
+    void require_1x1_factors_block() {
+        SLU_REQUIRE(!zmode, "solve_block: not on 3D plans (the block sweep runs on 1x1 plans only)");
+        SLU_REQUIRE(!xmode, "solve_block: not on a %dx%d grid (the block sweep has no exchanges; "
+                    "1x1 plans only)", Pr, Pc);
+        SLU_REQUIRE(vstate == 2, "solve_block: the device storage holds no factors (factor first)");
     }
 
     // ---- 2D grids: the distributed supernodal solve of pdgstrs
@@ -3701,7 +3663,11 @@ struct Plan : PlanBase {
     DevBuf<T> d_sv_slot;
     vector<int> sv_own;                  // per supernode: this rank is the diagonal owner
 
-    void build_solve_2d() {
+    // The tables of every sweep, on 1x1 plans and grids alike.  A 1x1 plan
+    // is the grid whose one rank owns every supernode: the panel of L(:,k)
+    // starts below the W(k) rows of the diagonal block, and the exchange
+    // lists (zero, adds, sv_red) come out empty.
+    void build_solve() {
         const int nl = (int)bylev.size();
         vector<SvDiag> dg(nsupers), pan(nsupers), lvl;
         vector<i64> roff(nsupers, 0), coff(nsupers, 0);
@@ -3720,14 +3686,16 @@ struct Plan : PlanBase {
             SvDiag pd = d;
             pd.pad = 0;
             roff[k] = (i64)rows.size();
-            if (lcol && lidx[k]) {
+            const bool held = lcol && lidx[k]; // the diagonal block is part of L(:,k): its owner holds the column
+            SLU_REQUIRE(held ? lval_off[k / Pc] >= 0 : !own, "supernode %d has no L column block", k);
+            if (held) {
                 const int ljb = k / Pc;
-                SLU_REQUIRE(lval_off[ljb] >= 0, "supernode %d: no L column block", k);
                 d.voff = lval_off[ljb];
                 d.ld = lval_ld[ljb];
                 int m = 0, r0 = 0;
                 lrows(k, m, r0);
                 SLU_REQUIRE(r0 == (own ? W(k) : 0), "supernode %d: diagonal block rows %d", k, r0);
+                SLU_REQUIRE(m == d.ld - r0, "supernode %d: panel rows", k);
                 pd.voff = lval_off[ljb] + r0;
                 pd.ld = lval_ld[ljb];
                 pd.pad = m;
@@ -3831,36 +3799,28 @@ struct Plan : PlanBase {
         X.flush();
     }
 
+    // sweep_nr<1> on the replicated xv, with the exchanges of each level
     void sweep_2d(T *xv) {
         const int nl = (int)bylev.size();
+        const i64 ldx = n;
         X.s = stream;
         const unsigned nz = (unsigned)(nsupers - std::accumulate(sv_own.begin(), sv_own.end(), 0));
-        if (nz) hipLaunchKernelGGL(k_sv_add<T>, dim3(nz), dim3(256), 0, stream, d_sv_zero.p, xv, (const T *)nullptr);
+        auto zero_others = [&] { // the block rows of other owners
+            if (nz) hipLaunchKernelGGL(k_sv_add<T>, dim3(nz), dim3(256), 0, stream, d_sv_zero.p, xv, (const T *)nullptr);
+        };
+        zero_others();
         for (int L = 0; L < nl; ++L) { // L y = b
             sv_reduce(L, xv);
-            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_l_off[L + 1] - sv_l_off[L];
-            if (nd)
-                hipLaunchKernelGGL((k_sv_ldiag<T, 1>), dim3(nd), dim3(SVD_THREADS), 0, stream,
-                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xv, (i64)n, 1);
+            sv_diag(L, k_sv_ldiag<T, 1>, SVD_THREADS, xv, ldx, 1);
             sv_bcast(L, xv, true);
-            if (nc)
-                hipLaunchKernelGGL((k_sv_lpanel<T, 1>), dim3(nc), dim3(SV_THREADS), 0, stream,
-                                   d_sv_lch.p + sv_l_off[L], d_sv_pan.p, d_sv_roff.p,
-                                   d_sv_rows.p, d_L.p, xv, (i64)n, 1);
+            sv_lpan(L, k_sv_lpanel<T, 1>, SV_THREADS, xv, ldx, 1);
         }
         const bool fwd_only = getenv("SLU_SV_FWD_ONLY") != nullptr; // diagnostics: y = L^-1 b
-        if (nz && !fwd_only) hipLaunchKernelGGL(k_sv_add<T>, dim3(nz), dim3(256), 0, stream, d_sv_zero.p, xv, (const T *)nullptr);
+        if (!fwd_only) zero_others();
         for (int L = fwd_only ? -1 : nl - 1; L >= 0; --L) { // U x = y
-            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_u_off[L + 1] - sv_u_off[L];
-            if (nc)
-                hipLaunchKernelGGL((k_sv_upanel<T, 1>), dim3(nc), dim3(SV_THREADS), 0, stream,
-                                   d_sv_uch.p + sv_u_off[L], d_sv_diag.p, d_sv_coff.p,
-                                   d_sv_ncol.p, d_ucol_voff.p, d_ucol_fst.p, d_sv_gc.p,
-                                   d_U.p, xv, (i64)n, 1);
+            sv_upan(L, k_sv_upanel<T, 1>, SV_THREADS, xv, ldx, 1);
             sv_reduce(L, xv);
-            if (nd)
-                hipLaunchKernelGGL((k_sv_udiag<T, 1>), dim3(nd), dim3(SVD_THREADS), 0, stream,
-                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xv, (i64)n, 1);
+            sv_diag(L, k_sv_udiag<T, 1>, SVD_THREADS, xv, ldx, 1);
             sv_bcast(L, xv, false);
         }
         sv_gather(xv);
@@ -3881,59 +3841,39 @@ struct Plan : PlanBase {
         if (trans != SLU_NOTRANS) require_1x1_factors("solve_t");
         solve_op(trans, b, ldb, nrhs);
     }
+    // columns c0 .. c0 + nc of the host array b (ld ldb) to / from nc device
+    // vectors of n values at dv, on `stream`
+    void cols_h2d(T *dv, const void *b, i64 ldb, int c0, int nc) {
+        for (int q = 0; q < nc; ++q)
+            HIPCHK(hipMemcpyAsync(dv + (i64)q * n, (const HT *)b + (i64)(c0 + q) * ldb, (size_t)n * sizeof(T),
+                                  hipMemcpyHostToDevice, stream));
+    }
+    void cols_d2h(void *b, i64 ldb, int c0, int nc, const T *dv) {
+        for (int q = 0; q < nc; ++q)
+            HIPCHK(hipMemcpyAsync((HT *)b + (i64)(c0 + q) * ldb, dv + (i64)q * n, (size_t)n * sizeof(T),
+                                  hipMemcpyDeviceToHost, stream));
+    }
     void solve_op(int trans, void *b, int64_t ldb, int nrhs) {
         SLU_REQUIRE(!zmode, "solve: 3D plans hold the factors spread over the layers (gather them to a 2D plan)");
         SLU_REQUIRE(vstate == 2, "solve: the device storage holds no factors (factor first)");
         if (!sv_ready) build_solve();
-        if (xmode) {
-            SLU_REQUIRE(ldb >= n && nrhs >= 0, "solve: ldb %lld < n %d", (long long)ldb, n);
-            HIPCHK(hipStreamSynchronize(pstream));
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0));
-            HIPCHK(hipEventCreate(&e1));
-            float total = 0;
-            for (int j = 0; j < nrhs; ++j) {
-                HT *bj = (HT *)b + (i64)j * ldb;
-                HIPCHK(hipMemcpyAsync(d_sv_x.p, bj, (size_t)n * sizeof(T), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipEventRecord(e0, stream));
-                sweep_2d(d_sv_x.p);
-                HIPCHK(hipEventRecord(e1, stream));
-                HIPCHK(hipMemcpyAsync(bj, d_sv_x.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                float ms = 0;
-                HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-                total += ms;
-            }
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            stats.t_solve_ms = total;
-            return;
-        }
         SLU_REQUIRE(ldb >= n && nrhs >= 0, "solve: ldb %lld < n %d", (long long)ldb, n);
-        constexpr int NB = SvNr<T>::v;
-        if (nrhs > 1 && d_sv_x.n < (size_t)n * NB) d_sv_x.alloc((size_t)std::max(n, 1) * NB);
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
+        const int NB = xmode ? 1 : SvNr<T>::v; // grids: one right-hand side per sweep_2d
+        if (xmode) HIPCHK(hipStreamSynchronize(pstream));
+        else if (nrhs > 1 && d_sv_x.n < (size_t)n * NB) d_sv_x.alloc((size_t)std::max(n, 1) * NB);
+        EventTimer tm;
         float total = 0;
         for (int r0 = 0; r0 < nrhs; r0 += NB) {
             const int nr = std::min(NB, nrhs - r0);
-            for (int q = 0; q < nr; ++q)
-                HIPCHK(hipMemcpyAsync(d_sv_x.p + (i64)q * n, (HT *)b + (i64)(r0 + q) * ldb,
-                                      (size_t)n * sizeof(T), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipEventRecord(e0, stream));
-            sweep_op(trans, d_sv_x.p, n, nr);
-            HIPCHK(hipEventRecord(e1, stream));
-            for (int q = 0; q < nr; ++q)
-                HIPCHK(hipMemcpyAsync((HT *)b + (i64)(r0 + q) * ldb, d_sv_x.p + (i64)q * n,
-                                      (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream));
+            cols_h2d(d_sv_x.p, b, ldb, r0, nr);
+            tm.start(stream);
+            if (xmode) sweep_2d(d_sv_x.p);
+            else sweep_op(trans, d_sv_x.p, n, nr);
+            tm.stop(stream);
+            cols_d2h(b, ldb, r0, nr, d_sv_x.p);
             HIPCHK(hipStreamSynchronize(stream));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-            total += ms;
+            total += tm.ms();
         }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         stats.t_solve_ms = total;
     }
 
@@ -3945,36 +3885,18 @@ struct Plan : PlanBase {
         const int nl = (int)bylev.size();
         i64 nk = 0;
         for (int L = 0; L < nl; ++L) { // L Y = B
-            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_l_off[L + 1] - sv_l_off[L];
-            if (nd)
-                hipLaunchKernelGGL((k_svb_ldiag<T>), dim3(nd), dim3(SVB_DTHREADS), 0, stream,
-                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xb);
-            if (nc)
-                hipLaunchKernelGGL((k_svb_lpanel<T>), dim3(nc), dim3(SVB_LTHREADS), 0, stream,
-                                   d_sv_lch.p + sv_l_off[L], d_sv_pan.p, d_sv_roff.p,
-                                   d_sv_rows.p, d_L.p, xb);
-            nk += (nd > 0) + (nc > 0);
+            nk += sv_diag(L, k_svb_ldiag<T>, SVB_DTHREADS, xb);
+            nk += sv_lpan(L, k_svb_lpanel<T>, SVB_LTHREADS, xb);
         }
         for (int L = nl - 1; L >= 0; --L) { // U X = Y
-            const int nd = sv_d_off[L + 1] - sv_d_off[L], nc = sv_u_off[L + 1] - sv_u_off[L];
-            if (nc)
-                hipLaunchKernelGGL((k_svb_upanel<T>), dim3(nc), dim3(SV_THREADS), 0, stream,
-                                   d_sv_uch.p + sv_u_off[L], d_sv_diag.p, d_sv_coff.p,
-                                   d_sv_ncol.p, d_ucol_voff.p, d_ucol_fst.p, d_sv_gc.p,
-                                   d_U.p, xb);
-            if (nd)
-                hipLaunchKernelGGL((k_svb_udiag<T>), dim3(nd), dim3(SVB_DTHREADS), 0, stream,
-                                   d_sv_lvl.p + sv_d_off[L], d_L.p, xb);
-            nk += (nd > 0) + (nc > 0);
+            nk += sv_upan(L, k_svb_upanel<T>, SV_THREADS, xb);
+            nk += sv_diag(L, k_svb_udiag<T>, SVB_DTHREADS, xb);
         }
         HIPCHK(hipGetLastError());
         return nk;
     }
     void solve_block(void *b, int64_t ldb, int nrhs, int on_device) override {
-        SLU_REQUIRE(!zmode, "solve_block: not on 3D plans (the block sweep runs on 1x1 plans only)");
-        SLU_REQUIRE(!xmode, "solve_block: not on a %dx%d grid (the block sweep has no exchanges; "
-                    "1x1 plans only)", Pr, Pc);
-        SLU_REQUIRE(vstate == 2, "solve_block: the device storage holds no factors (factor first)");
+        require_1x1_factors_block();
         SLU_REQUIRE(ldb >= n && nrhs >= 0, "solve_block: ldb %lld < n %d or nrhs %d < 0", (long long)ldb, n, nrhs);
         svb_passes = 0;
         svb_launches = 0;
@@ -3986,37 +3908,25 @@ struct Plan : PlanBase {
         const size_t nn = (size_t)n;
         if (d_svb_x.n < nn * NRB) d_svb_x.alloc(nn * NRB);
         if (!on_device && d_svb_stage.n < nn * NRB) d_svb_stage.alloc(nn * NRB);
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
+        EventTimer tm;
         const unsigned tb = (unsigned)((n + SVB_TR_ROWS - 1) / SVB_TR_ROWS);
         float total = 0;
         for (int r0 = 0; r0 < nrhs; r0 += NRB) {
             const int nr = std::min(NRB, nrhs - r0);
             T *cols = on_device ? (T *)b + (i64)r0 * ldb : d_svb_stage.p; // the pass's columns on the device
             const i64 ldc = on_device ? ldb : (i64)n;
-            if (!on_device)
-                for (int q = 0; q < nr; ++q)
-                    HIPCHK(hipMemcpyAsync(cols + (i64)q * n, (HT *)b + (i64)(r0 + q) * ldb,
-                                          nn * sizeof(T), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipEventRecord(e0, stream));
+            if (!on_device) cols_h2d(cols, b, ldb, r0, nr);
+            tm.start(stream);
             hipLaunchKernelGGL((k_svb_in<T>), dim3(tb), dim3(256), 0, stream, (const T *)cols, ldc, n, nr, d_svb_x.p);
             svb_launches += 2 + sweep_block(d_svb_x.p);
             hipLaunchKernelGGL((k_svb_out<T>), dim3(tb), dim3(256), 0, stream, (const T *)d_svb_x.p, n, nr, cols, ldc);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(e1, stream));
-            if (!on_device)
-                for (int q = 0; q < nr; ++q)
-                    HIPCHK(hipMemcpyAsync((HT *)b + (i64)(r0 + q) * ldb, cols + (i64)q * n,
-                                          nn * sizeof(T), hipMemcpyDeviceToHost, stream));
+            tm.stop(stream);
+            if (!on_device) cols_d2h(b, ldb, r0, nr, cols);
             HIPCHK(hipStreamSynchronize(stream));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-            total += ms;
+            total += tm.ms();
             ++svb_passes;
         }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         svb_ms = total;
         stats.t_solve_ms = total;
     }
@@ -4065,20 +3975,26 @@ struct Plan : PlanBase {
         HIPCHK(hipDeviceSynchronize());
     }
 
+    // this process row's partial residual rows r (elements of rsz bytes) and
+    // partial sums d_rf_s to the diagonal owners' slots sr and d_rf_ss
+    void rf_reduce(void *r, void *sr, size_t rsz) {
+        for (const auto &q : rf_secs) {
+            const int k = (int)q[0], c = (int)q[1], oc = k % Pc;
+            const size_t w = (size_t)W(k);
+            void *br = mycol == c ? (char *)r + xsup[k] * rsz : mycol == oc ? (char *)sr + q[2] * rsz : nullptr;
+            void *bs = mycol == c ? (void *)(d_rf_s.p + xsup[k]) : mycol == oc ? (void *)(d_rf_ss.p + q[2]) : nullptr;
+            X.section(G_ROW, c, 1u << oc, br, w * rsz);
+            X.section(G_ROW, c, 1u << oc, bs, w * sizeof(double));
+        }
+        X.flush();
+    }
+
     double resid_2d(double safe1, double safe2) {
         const unsigned rb = (unsigned)((n + 255) / 256);
         X.s = stream;
         hipLaunchKernelGGL(k_resid_part<T>, dim3(rb), dim3(256), 0, stream, d_rp.p, d_rc.p, d_re.p,
                            a_fact, d_rf_x.p, d_rf_r.p, d_rf_s.p, n);
-        for (const auto &q : rf_secs) {
-            const int k = (int)q[0], c = (int)q[1], oc = k % Pc;
-            const size_t w = (size_t)W(k);
-            void *br = mycol == c ? (void *)(d_rf_r.p + xsup[k]) : mycol == oc ? (void *)(d_rf_sr.p + q[2]) : nullptr;
-            void *bs = mycol == c ? (void *)(d_rf_s.p + xsup[k]) : mycol == oc ? (void *)(d_rf_ss.p + q[2]) : nullptr;
-            X.section(G_ROW, c, 1u << oc, br, w * sizeof(T));
-            X.section(G_ROW, c, 1u << oc, bs, w * sizeof(double));
-        }
-        X.flush();
+        rf_reduce(d_rf_r.p, d_rf_sr.p, sizeof(T));
         HIPCHK(hipMemsetAsync(d_rf_berr.p, 0, sizeof(unsigned long long), stream));
         if (!rf_rows_h.empty())
             hipLaunchKernelGGL(k_resid_fin<T>, dim3((unsigned)rf_rows_h.size()), dim3(256), 0, stream,
@@ -4125,6 +4041,46 @@ struct Plan : PlanBase {
         csc_ready = true;
     }
 
+    // r <- op(B)^-1 r with the device factors (grids: R from its owners to
+    // every rank first, then the 2D solve)
+    void correct(int trans, T *r) {
+        if (xmode) {
+            sv_gather(r);
+            sweep_2d(r);
+        } else {
+            sweep_op(trans, r);
+        }
+    }
+
+    // The loop of pdgsrfs over right-hand sides and steps; t_refine_ms.
+    // load(j) puts b and x of column j on the device, resid() returns berr of
+    // the current x, step() adds one correction to x, store(j) copies x back.
+    template <typename Ld, typename Rs, typename Cx, typename St>
+    void refine_loop(double eps, int nrhs, double *berr, int *steps, Ld load, Rs resid, Cx step, St store) {
+        EventTimer tm;
+        HIPCHK(hipStreamSynchronize(pstream));
+        tm.start(stream);
+        for (int j = 0; j < nrhs; ++j) {
+            load(j);
+            int count = 0;
+            double lstres = 3.0, be = 0.0;
+            while (true) {
+                be = resid();
+                if (!(be > eps && be * 2 <= lstres && count < 20)) break;
+                step();
+                lstres = be;
+                ++count;
+            }
+            store(j);
+            HIPCHK(hipStreamSynchronize(stream));
+            if (berr) berr[j] = be;
+            if (steps) steps[j] = count;
+        }
+        tm.stop(stream);
+        HIPCHK(hipStreamSynchronize(stream));
+        stats.t_refine_ms = tm.ms();
+    }
+
     void refine_op(int trans, const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) {
         SLU_REQUIRE(!zmode, "refine: not on 3D plans");
         SLU_REQUIRE(vstate == 2, "refine: the device storage holds no factors (factor first)");
@@ -4144,59 +4100,35 @@ struct Plan : PlanBase {
         if (xmode && rf_rows_h.empty() && rf_secs.empty()) build_refine_2d();
         if (trans && !csc_ready) build_csc();
         const unsigned rb = (unsigned)((n + 255) / 256);
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipStreamSynchronize(pstream));
-        HIPCHK(hipEventRecord(e0, stream));
-        for (int j = 0; j < nrhs; ++j) {
-            const HT *hb = (const HT *)b + (i64)j * ld;
-            HT *hx = (HT *)x + (i64)j * ld;
-            HIPCHK(hipMemcpyAsync(d_rf_b.p, hb, (size_t)n * sizeof(T), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(d_rf_x.p, hx, (size_t)n * sizeof(T), hipMemcpyHostToDevice, stream));
-            int count = 0;
-            double lstres = 3.0, be = 0.0;
-            while (true) {
-                if (xmode) {
-                    be = resid_2d(safe1, safe2);
-                } else {
-                    HIPCHK(hipMemsetAsync(d_rf_berr.p, 0, sizeof(unsigned long long), stream));
-                    if (trans)
-                        hipLaunchKernelGGL(k_resid_t<T>, dim3(rb), dim3(256), 0, stream, d_csc_lo.p, d_csc_hi.p,
-                                           d_csc_ci.p, a_fact, d_rf_x.p, d_rf_b.p, d_rf_r.p, n, safe1, safe2,
-                                           d_rf_berr.p, (int)(trans == SLU_CONJ));
-                    else
-                        hipLaunchKernelGGL(k_resid<T>, dim3(rb), dim3(256), 0, stream, d_rp.p, d_rc.p, d_re.p,
-                                           a_fact, d_rf_x.p, d_rf_b.p, d_rf_r.p, n, safe1, safe2, d_rf_berr.p);
-                    HIPCHK(hipGetLastError());
-                    unsigned long long bits = 0;
-                    HIPCHK(hipMemcpyAsync(&bits, d_rf_berr.p, sizeof bits, hipMemcpyDeviceToHost, stream));
-                    HIPCHK(hipStreamSynchronize(stream));
-                    memcpy(&be, &bits, sizeof be);
-                }
-                if (!(be > eps && be * 2 <= lstres && count < 20)) break;
-                if (xmode) {
-                    sv_gather(d_rf_r.p); // R from its owners to every rank, then the 2D solve
-                    sweep_2d(d_rf_r.p);
-                } else {
-                    sweep_op(trans, d_rf_r.p);
-                }
+        refine_loop(
+            eps, nrhs, berr, steps,
+            [&](int j) {
+                cols_h2d(d_rf_b.p, b, ld, j, 1);
+                cols_h2d(d_rf_x.p, x, ld, j, 1);
+            },
+            [&] {
+                if (xmode) return resid_2d(safe1, safe2);
+                HIPCHK(hipMemsetAsync(d_rf_berr.p, 0, sizeof(unsigned long long), stream));
+                if (trans)
+                    hipLaunchKernelGGL(k_resid_t<T>, dim3(rb), dim3(256), 0, stream, d_csc_lo.p, d_csc_hi.p,
+                                       d_csc_ci.p, a_fact, d_rf_x.p, d_rf_b.p, d_rf_r.p, n, safe1, safe2,
+                                       d_rf_berr.p, (int)(trans == SLU_CONJ));
+                else
+                    hipLaunchKernelGGL(k_resid<T>, dim3(rb), dim3(256), 0, stream, d_rp.p, d_rc.p, d_re.p,
+                                       a_fact, d_rf_x.p, d_rf_b.p, d_rf_r.p, n, safe1, safe2, d_rf_berr.p);
+                HIPCHK(hipGetLastError());
+                unsigned long long bits = 0;
+                HIPCHK(hipMemcpyAsync(&bits, d_rf_berr.p, sizeof bits, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                double be;
+                memcpy(&be, &bits, sizeof be);
+                return be;
+            },
+            [&] {
+                correct(trans, d_rf_r.p);
                 hipLaunchKernelGGL(k_axpy1<T>, dim3(rb), dim3(256), 0, stream, d_rf_x.p, d_rf_r.p, n);
-                lstres = be;
-                ++count;
-            }
-            HIPCHK(hipMemcpyAsync(hx, d_rf_x.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            if (berr) berr[j] = be;
-            if (steps) steps[j] = count;
-        }
-        HIPCHK(hipEventRecord(e1, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        stats.t_refine_ms = ms;
+            },
+            [&](int j) { cols_d2h(x, ld, j, 1, d_rf_x.p); });
     }
 
     // Mixed-precision refinement of an fp32 plan (refine_d2.h): the loop of
@@ -4218,15 +4150,7 @@ struct Plan : PlanBase {
             X.s = stream;
             hipLaunchKernelGGL(k_resid_part_d2, dim3(rb), dim3(256), 0, stream, d_rp.p, d_rc.p, d_re.p,
                                a_fact64, d_d2_x.p, d_d2_r.p, d_rf_s.p, n);
-            for (const auto &q : rf_secs) { // the sections of resid_2d, r_p as doubles
-                const int k = (int)q[0], c = (int)q[1], oc = k % Pc;
-                const size_t w = (size_t)W(k);
-                void *br = mycol == c ? (void *)(d_d2_r.p + xsup[k]) : mycol == oc ? (void *)(d_d2_sr.p + q[2]) : nullptr;
-                void *bs = mycol == c ? (void *)(d_rf_s.p + xsup[k]) : mycol == oc ? (void *)(d_rf_ss.p + q[2]) : nullptr;
-                X.section(G_ROW, c, 1u << oc, br, w * sizeof(double));
-                X.section(G_ROW, c, 1u << oc, bs, w * sizeof(double));
-            }
-            X.flush();
+            rf_reduce(d_d2_r.p, d_d2_sr.p, sizeof(double)); // the sections of resid_2d, r_p as doubles
             if (!rf_rows_h.empty())
                 hipLaunchKernelGGL(k_resid_fin_d2, dim3((unsigned)rf_rows_h.size()), dim3(256), 0, stream,
                                    d_rf_rows.p, d_d2_b.p, d_d2_r.p, d_rf_s.p, d_d2_sr.p, d_rf_ss.p, safe1,
@@ -4268,46 +4192,26 @@ struct Plan : PlanBase {
                 if (d_d2_sr.n != d_rf_sr.n) d_d2_sr.alloc(d_rf_sr.n);
             }
             const unsigned rb = (unsigned)((n + 255) / 256);
-            hipEvent_t e0, e1;
-            HIPCHK(hipEventCreate(&e0));
-            HIPCHK(hipEventCreate(&e1));
-            HIPCHK(hipStreamSynchronize(pstream));
-            HIPCHK(hipEventRecord(e0, stream));
-            for (int j = 0; j < nrhs; ++j) {
-                double *hx = x + (i64)j * ld;
-                HIPCHK(hipMemcpyAsync(d_d2_b.p, b + (i64)j * ld, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
-                HIPCHK(hipMemcpyAsync(d_d2_x.p, hx, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream));
-                int count = 0;
-                double lstres = 3.0, mx[2] = {0.0, 0.0};
-                while (true) {
+            const size_t nb = (size_t)n * sizeof(double);
+            double mx[2] = {0.0, 0.0};
+            refine_loop(
+                eps, nrhs, berr, steps,
+                [&](int j) {
+                    HIPCHK(hipMemcpyAsync(d_d2_b.p, b + (i64)j * ld, nb, hipMemcpyHostToDevice, stream));
+                    HIPCHK(hipMemcpyAsync(d_d2_x.p, x + (i64)j * ld, nb, hipMemcpyHostToDevice, stream));
+                },
+                [&] {
                     resid_d2(safe1, safe2, mx);
-                    const double be = mx[0], rmax = mx[1];
-                    if (!(be > eps && be * 2 <= lstres && count < 20)) break;
+                    return mx[0];
+                },
+                [&] {
                     int e = 0;
-                    if (rmax > 0.0 && std::isfinite(rmax)) (void)frexp(rmax, &e);
+                    if (mx[1] > 0.0 && std::isfinite(mx[1])) (void)frexp(mx[1], &e);
                     hipLaunchKernelGGL(k_scale_cvt_d2, dim3(rb), dim3(256), 0, stream, d_d2_r.p, d_rf_r.p, n, e);
-                    if (xmode) {
-                        sv_gather(d_rf_r.p); // the owners' rows of r32 to every rank, then the 2D solve
-                        sweep_2d(d_rf_r.p);
-                    } else {
-                        sweep(d_rf_r.p);
-                    }
+                    correct(SLU_NOTRANS, d_rf_r.p); // the owners' rows of r32 on grids
                     hipLaunchKernelGGL(k_axpy_d2, dim3(rb), dim3(256), 0, stream, d_d2_x.p, d_rf_r.p, n, e);
-                    lstres = be;
-                    ++count;
-                }
-                HIPCHK(hipMemcpyAsync(hx, d_d2_x.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                if (berr) berr[j] = mx[0];
-                if (steps) steps[j] = count;
-            }
-            HIPCHK(hipEventRecord(e1, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            stats.t_refine_ms = ms;
+                },
+                [&](int j) { HIPCHK(hipMemcpyAsync(x + (i64)j * ld, d_d2_x.p, nb, hipMemcpyDeviceToHost, stream)); });
         } else {
             throw Error(fmt("refine_d2: fp32 plans only, this plan's dtype is %s", dtype_name()));
         }
@@ -4363,11 +4267,9 @@ struct Plan : PlanBase {
                                jlast, d_rc_out.p);
             return fetch();
         };
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
+        EventTimer tm;
         HIPCHK(hipStreamSynchronize(pstream));
-        HIPCHK(hipEventRecord(e0, stream));
+        tm.start(stream);
         HIPCHK(hipMemsetAsync(d_rc_sgn.p, 0, nn * sizeof(T), stream));
         double est = 0.0;
         bool ok = n > 0;
@@ -4403,14 +4305,10 @@ struct Plan : PlanBase {
                 if (temp > est) est = temp;
             }
         }
-        HIPCHK(hipEventRecord(e1, stream));
+        tm.stop(stream);
         HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         rc_sweeps = sweeps;
-        rc_ms = ms;
+        rc_ms = tm.ms();
         *rc = (ok && anorm != 0.0 && std::isfinite(anorm) && est != 0.0) ? 1.0 / (anorm * est) : 0.0;
     }
 
@@ -4577,24 +4475,18 @@ struct Plan : PlanBase {
     template <typename F> void fill_storage(F &&launch) {
         vstate = 1;
         host_current = false;
-        hipEvent_t e0, e1;
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
+        EventTimer tm;
         HIPCHK(hipStreamSynchronize(pstream));
-        HIPCHK(hipEventRecord(e0, stream));
+        tm.start(stream);
         if (d_L.n) HIPCHK(hipMemsetAsync(d_L.p, 0, d_L.bytes(), stream));
         if (d_U.n) HIPCHK(hipMemsetAsync(d_U.p, 0, d_U.bytes(), stream));
         if (a_nnz) {
             launch((unsigned)std::min<i64>((a_nnz + FILL_THREADS - 1) / FILL_THREADS, 65536));
             HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipEventRecord(e1, stream));
+        tm.stop(stream);
         HIPCHK(hipStreamSynchronize(stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        stats.t_fill_ms = ms;
+        stats.t_fill_ms = tm.ms();
     }
 
     static const char *dtype_name() {
