@@ -11,7 +11,9 @@ an exact pivot value at any column.
 
 ``dense_lu_ref`` is an unpivoted right-looking LU in ``np.longdouble`` with
 the tiny-pivot rule of oracle/oracle_impl.h; ``lu_to_dense`` scatters a
-factored 1x1 LUstruct into a dense matrix to compare with it.
+factored 1x1 LUstruct into a dense matrix to compare with it; ``ld_solve``
+solves with its factors (plain, transposed, conjugate transposed) in long
+double, the reference of the solve kernels' tests.
 """
 import functools
 
@@ -39,6 +41,19 @@ FAMILIES = {
     # full 128-row Schur tile, and one more tile of a single row
     "schur128_star": _STAR([96, 70], 192),
     "schur129_star": _STAR([96, 70], 194),
+    # the solve kernels' edges (tests/test_gpu_solve_shapes.py): width 1 and the
+    # G = 1, 2, 8 lane groups of k_sv_utpanel, widths around the 16-column
+    # complex panel and the 16-row MFMA fragments (w % 16 in {0, 1, 15})
+    "frag_star": _STAR([1, 2, 7, 15, 16, 47, 48, 49], 96),
+    # the leaves' L panels have exactly 256 / 257 rows (2/3 of the root): one
+    # full 256-row chunk of the panel kernels, and a second chunk of one row
+    "lpanel256_star": _STAR([40, 100], 384),
+    "lpanel257_star": _STAR([40, 100], 386),
+    # a block of the largest width with L and U panels: every thread of the
+    # 512-thread diagonal solves is live; 511: a partial last panel of 31
+    # (complex: 15) columns that starts mid-wave in the last wavefront
+    "max_inner": _CHAIN([512, 200]),
+    "max511_inner": _CHAIN([511, 150]),
 }
 MAXSUP = 512
 
@@ -145,6 +160,46 @@ def dense_lu_ref(V, thresh=None):
         if j + 1 < n:
             M[j + 1:, j + 1:] -= np.outer(M[j + 1:, j], M[j, j + 1:])
     return M, info, tiny
+
+
+def ld_solve(R, b, trans=None):
+    """Solve op(B) x = b in long double with the packed factors of
+    dense_lu_ref (L strictly lower and unit, U upper), column-oriented.
+    trans None: B x = b (L forward, U backward); "T": B^T x = b (U^T forward
+    along U's rows, L^T backward along L's rows); "C": the same on conj(R).
+    b: (n,) or (n, nrhs); returns x of b's shape in R's dtype."""
+    assert trans in (None, "T", "C")
+    if trans == "C":
+        R = np.conj(R)
+    n = R.shape[0]
+    b = np.asarray(b)
+    x = np.array(b.reshape(n, -1), dtype=R.dtype)
+    if trans is None:
+        for j in range(n - 1):                  # L y = b
+            x[j + 1:] -= np.outer(R[j + 1:, j], x[j])
+        for j in range(n - 1, -1, -1):          # U x = y
+            x[j] /= R[j, j]
+            x[:j] -= np.outer(R[:j, j], x[j])
+    else:
+        for j in range(n):                      # U^T z = b
+            x[j] /= R[j, j]
+            x[j + 1:] -= np.outer(R[j, j + 1:], x[j])
+        for j in range(n - 1, 0, -1):           # L^T x = z
+            x[:j] -= np.outer(R[j, :j], x[j])
+    return x.reshape(b.shape)
+
+
+def ld_inverse(R):
+    """B^-1 in long double from the packed factors: ld_solve(R, I), with the
+    forward sweep kept to the columns of L^-1 that are non-zero so far."""
+    n = R.shape[0]
+    x = np.eye(n, dtype=R.dtype)
+    for j in range(n - 1):
+        x[j + 1:, :j + 1] -= np.outer(R[j + 1:, j], x[j, :j + 1])
+    for j in range(n - 1, -1, -1):
+        x[j] /= R[j, j]
+        x[:j] -= np.outer(R[:j, j], x[j])
+    return x
 
 
 def lu_to_dense(lu, n):
@@ -264,3 +319,78 @@ def reference(family, dtype, pivot=None, replace_tiny=False, seed=7):
     A, S, V, an = case(family, dtype, pivot, seed)
     B = A.permuted(S.perm_c).to_dense()
     return dense_lu_ref(B, S_EPS * norm_for(an, True) if replace_tiny else None)
+
+
+# ---- the yardstick of the solve tests: the CPU pipeline against ld_solve
+@functools.lru_cache(maxsize=None)
+def oracle_lu(family, dtype):
+    """A family's 1x1 LUstruct holding the oracle's factors in the family's
+    own dtype (cached, read-only)."""
+    import pyoracle
+    A, S, V, an = case(family, dtype)
+    lu = S.distribute()
+    o = pyoracle.oracle_factor([lu], 1, 1, A.n, False, an)
+    assert o["info"] == 0 and o["tiny"] == 0
+    return lu
+
+
+def rhs(family, dtype, ncols=33):
+    """ncols random right-hand sides rounded to the family's dtype (cached,
+    read-only, Fortran order)."""
+    return _rhs(family, dtype, ncols)
+
+
+def ld_solution(family, dtype, trans=None, ncols=33):
+    """ld_solve of rhs(family, dtype, ncols) with the family's long-double
+    factors (cached, read-only)."""
+    return _ld_solution(family, dtype, trans, ncols)
+
+
+def cpu_errors(family, dtype, trans=None, ncols=33):
+    """Per column, the error against ld_solution of the CPU pipeline on the
+    same right-hand sides and op: the oracle's factors in the family's dtype,
+    then the host supernodal solve of lusolve / lusolve_t (which promotes to
+    fp64).  Cached, read-only."""
+    return _cpu_errors(family, dtype, trans, ncols)
+
+
+@functools.lru_cache(maxsize=None)
+def _rhs(family, dtype, ncols, seed=11):
+    """ncols random right-hand sides rounded to the family's dtype (cached,
+    read-only, Fortran order)."""
+    n = case(family, dtype)[0].n
+    rng = np.random.default_rng(seed)
+    b = rng.standard_normal((n, ncols))
+    if dtype == SLU_Z:
+        b = b + 1j * rng.standard_normal((n, ncols))
+    b = np.asfortranarray(b.astype(DTYPES[dtype]))
+    b.setflags(write=False)
+    return b
+
+
+@functools.lru_cache(maxsize=None)
+def _ld_solution(family, dtype, trans, ncols):
+    x = ld_solve(reference(family, dtype)[0], rhs(family, dtype, ncols), trans)
+    x.setflags(write=False)
+    return x
+
+
+def col_errors(x, xref):
+    """Normwise error per column, max|x - xref| / max|xref|, in xref's precision."""
+    x = np.asarray(x).reshape(xref.shape[0], -1)
+    xr = xref.reshape(xref.shape[0], -1)
+    if not np.isfinite(x).all():
+        return np.full(xr.shape[1], np.inf)
+    return (np.abs(x.astype(xr.dtype) - xr).max(axis=0) / np.abs(xr).max(axis=0)).astype(np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def _cpu_errors(family, dtype, trans, ncols):
+    from lusolve_t import solve_1x1, solve_1x1_t
+    lu = oracle_lu(family, dtype)
+    b = rhs(family, dtype, ncols)
+    cols = [solve_1x1(lu, b[:, r]) if trans is None else solve_1x1_t(lu, b[:, r], conj=trans == "C")
+            for r in range(ncols)]
+    e = col_errors(np.stack(cols, axis=1), ld_solution(family, dtype, trans, ncols))
+    e.setflags(write=False)
+    return e

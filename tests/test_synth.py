@@ -11,11 +11,17 @@ reference, checked on the CPU before the GPU tests lean on them
 * planted zero and tiny pivots: info and the tiny count of the oracle and of
   dense_lu_ref agree, and so do the factors, as far as they are well defined
   (synth.final_upto; replaced pivots are factored with synth.PIVOT_ANORM, where
-  the reasons are written down).
+  the reasons are written down);
+* synth.ld_solve (N / T / C) leaves a residual below 1e-17 against the dense
+  matrix, and the CPU pipeline the solve tests are judged against
+  (tests/test_gpu_solve_shapes.py: the oracle's factors in the family's dtype,
+  then lusolve / lusolve_t) agrees with it within test_oracle.TOL.
 
 Largest oracle-vs-long-double error seen on these families (max over L and U
 of max|oracle - ref| / max|ref|): d 2.8e-15, z 2.1e-15, s 1.4e-6; with the
-planted pivots d 2.7e-15, z 1.2e-15, s 1.0e-6.
+planted pivots d 2.7e-15, z 1.2e-15, s 1.0e-6.  Largest error of the CPU solve
+pipeline against ld_solve (normwise per column, 3 columns, N / T / C): d
+1.9e-15, z 2.0e-15, s 8.5e-7; ld_solve's own residual at most 4.4e-19.
 """
 import numpy as np
 import pytest
@@ -67,6 +73,59 @@ def test_schur_edge_families_have_the_panel_heights(family, rows):
         w = lu.xsup[k + 1] - lu.xsup[k]
         assert lu.Lidx[lu.Loff[k] + 1] - w == rows
         assert sum(1 for kk, _ in synth.u_first_rows(lu) if kk == k) >= 128
+
+
+@pytest.mark.parametrize("family,rows", [("lpanel256_star", 256), ("lpanel257_star", 257)])
+def test_lpanel_edge_families_have_the_panel_heights(family, rows):
+    """The leaves' L panels are exactly 256 / 257 rows high: one full 256-row
+    chunk of the solve's panel kernels, and a second chunk of a single row."""
+    lu = synth.case(family, 0)[1].distribute()
+    for k in range(lu.nsupers - 1):
+        w = lu.xsup[k + 1] - lu.xsup[k]
+        assert lu.Lidx[lu.Loff[k] + 1] - w == rows
+
+
+OPS = [None, "T", "C"]
+
+
+@pytest.mark.parametrize("trans", OPS)
+@pytest.mark.parametrize("dtype", [0, 1, 2])
+@pytest.mark.parametrize("family", ["frag_star", "max_inner"])
+def test_ld_solve_residual(family, dtype, trans):
+    """||op(A) x - b||_inf / (||op(A)||_inf ||x||_inf) of ld_solve in long
+    double against the dense V, vector and matrix b."""
+    A, S, V, an = synth.case(family, dtype)
+    R = synth.reference(family, dtype)[0]
+    M = np.array(V, dtype=R.dtype)
+    M = M.T if trans else M
+    M = np.conj(M) if trans == "C" else M
+    b = synth.rhs(family, dtype)[:, :3]
+    x = synth.ld_solve(R, b, trans)
+    assert x.shape == b.shape and x.dtype == R.dtype
+    res = (np.abs(M @ x - b).max(axis=0) / (np.abs(M).sum(axis=1).max() * np.abs(x).max(axis=0))).max()
+    print(f"{family} dtype {dtype} {trans}: residual {float(res):.3e}")
+    assert res < 1e-17, res
+    x0 = synth.ld_solve(R, b[:, 0], trans)
+    assert x0.shape == (A.n,) and np.array_equal(x0, x[:, 0])
+    if dtype != 2:
+        assert np.array_equal(synth.ld_solve(R, b, "C"), synth.ld_solve(R, b, "T"))
+    if family == "frag_star" and trans is None:   # ld_inverse is ld_solve of the identity
+        assert np.array_equal(synth.ld_inverse(R), synth.ld_solve(R, np.eye(A.n)))
+
+
+@pytest.mark.parametrize("family,dtype", FAMILY_DTYPES)
+def test_cpu_pipeline_against_long_double(family, dtype):
+    """The yardstick of tests/test_gpu_solve_shapes.py: the oracle's factors
+    in the family's dtype, the host solves of lusolve / lusolve_t on them,
+    normwise error per column against ld_solve (3 columns, N / T / C)."""
+    worst = 0.0
+    for trans in OPS:
+        if trans == "C" and dtype != 2:
+            continue
+        e = synth.cpu_errors(family, dtype, trans, 3)
+        print(f"{family} dtype {dtype} {trans}: CPU pipeline vs long double {e.max():.3e}")
+        worst = max(worst, float(e.max()))
+    assert worst < TOL[dtype], worst
 
 
 def test_pivot_keeps_the_partition():
