@@ -312,6 +312,41 @@ int slu_plan_rcond_info(const slu_plan *p, int *sweeps, double *ms);
 int slu_plan_solve_block(slu_plan *p, void *b, int64_t ldb, int nrhs, int on_device);
 /* passes over the factors, kernel launches and device ms of the last call */
 int slu_plan_solve_block_info(const slu_plan *p, int *passes, int64_t *launches, double *ms);
+/* Block iterative refinement (1x1 plans; 2D and 3D plans refused): the loop
+ * of slu_plan_refine (refine_block) / slu_plan_refine_d2 (refine_block_d2)
+ * on a pass of SVB_NR columns at once (32, 16 in complex;
+ * csrc/refine_block.h).  Each step of a pass is one residual kernel over all
+ * of its columns, one block sweep of slu_plan_solve_block and one copy of
+ * the columns' berr to the host.  Per column the semantics are those of the
+ * per-column call: same eps, safmin, SAFE1/SAFE2 guards and at most 20
+ * steps; a column continues while berr > eps and 2 berr <= lstres; a NaN
+ * wins the max; refine_block_d2 normalises each column's residual by its own
+ * power of two, rmax = m 2^e.  A column that has stopped is frozen: the later
+ * steps of the pass, which run for its neighbours, do not change its x
+ * (steps[j] == 0: x[:, j] comes back bit for bit), and berr[j] is the
+ * backward error of the returned x[:, j].  A pass ends when all its columns
+ * have stopped.
+ * b, x: column-major, ld >= n, of the plan's element type (refine_block) or
+ * fp64 (refine_block_d2, fp32 plans only); on_device as in
+ * slu_plan_solve_block, for both.  b is never written; rows >= n and columns
+ * >= nrhs of x are never written.  berr[nrhs], steps[nrhs]: host arrays, may
+ * be NULL.  refine_block needs the A of slu_plan_fill_a and refuses factors
+ * of a slu_plan_fill_a_d2; refine_block_d2 needs the latter.
+ * Working buffers: X, B and R of a pass, each n rows of SVB_NR values
+ * (row-major) of the plan's type, fp64 for refine_block_d2 -- 3 x 256 MB at
+ * n = 10^6 in fp64 --, allocated at the first call and kept; refine_block_d2
+ * sweeps in slu_plan_solve_block's fp32 buffer.  A host array's columns are
+ * staged through R.  Nothing dispatches here automatically.  t_refine_ms in
+ * the stats is the device time of the call, as for slu_plan_refine.
+ * refine_block_info, of the last call of either: passes =
+ * ceil(nrhs / SVB_NR), sweeps = block sweeps = the sum over the passes of
+ * the largest steps[j] of the pass, resids = residual launches = sweeps +
+ * passes, and the device ms. */
+int slu_plan_refine_block(slu_plan *p, const void *b, void *x, int64_t ld, int nrhs,
+                          int on_device, double *berr, int *steps);
+int slu_plan_refine_block_d2(slu_plan *p, const double *b, double *x, int64_t ld, int nrhs,
+                             int on_device, double *berr, int *steps);
+int slu_plan_refine_block_info(const slu_plan *p, int *passes, int *sweeps, int *resids, double *ms);
 /* Schedule-only plans: replay every level's exchange phases of
  * slu_plan_factor through the communicator on host buffers; each received
  * section is checked byte for byte against what its root wrote.  Collective;
@@ -345,7 +380,7 @@ typedef struct {
                                   takes part in (as root or receiver) per factor */
     double t_solve_ms;         /* device time of the last slu_plan_solve / solve_t / solve_block */
     double t_fill_ms;          /* device time of the last slu_plan_fill_a */
-    double t_refine_ms;        /* device time of the last slu_plan_refine / refine_t */
+    double t_refine_ms;        /* device time of the last slu_plan_refine / refine_t / refine_block */
     /* host wall times of the drop-in path (ms) */
     double t_plan_ms;          /* slu_plan_create */
     double t_upload_ms;        /* H2D of the L/U values (overlapped with the

@@ -50,6 +50,7 @@
 #include "solve.h"
 #include "solve_block.h"
 #include "refine_d2.h"
+#include "refine_block.h"
 #include "hostio.h"
 #include "amalg.h"
 #include "amalg_dev.h"
@@ -341,6 +342,14 @@ struct PlanBase {
     // fp32 plans: fp64 values of A, fp64 residual and update (refine_d2.h)
     virtual void fill_a_d2(const double *a, int on_device) = 0;
     virtual void refine_d2(const double *b, double *x, int64_t ld, int nrhs, double *berr, int *steps) = 0;
+    // refine / refine_d2 on SvbNr columns per pass (1x1 plans; refine_block.h);
+    // passes, block sweeps, residual launches and device time of the call in rfb_*
+    virtual void refine_block(const void *b, void *x, int64_t ld, int nrhs, int on_device, double *berr,
+                              int *steps) = 0;
+    virtual void refine_block_d2(const double *b, double *x, int64_t ld, int nrhs, int on_device, double *berr,
+                                 int *steps) = 0;
+    int rfb_passes = 0, rfb_sweeps = 0, rfb_resids = 0;
+    double rfb_ms = 0;
     virtual void check_exchange(int64_t *nsec, int64_t *nbytes) = 0;
     virtual void gather_layers() { throw Error("gather_layers: not a 3D plan"); }
     virtual void adopt_factors() = 0; // upload host values that are already factors
@@ -3635,12 +3644,12 @@ struct Plan : PlanBase {
                     "rows and columns; 1x1 plans only)", what, Pr, Pc);
         SLU_REQUIRE(vstate == 2, "%s: the device storage holds no factors (factor first)", what);
     }
-    // the same rules in solve_block's words
-    void require_1x1_factors_block() {
-        SLU_REQUIRE(!zmode, "solve_block: not on 3D plans (the block sweep runs on 1x1 plans only)");
-        SLU_REQUIRE(!xmode, "solve_block: not on a %dx%d grid (the block sweep has no exchanges; "
-                    "1x1 plans only)", Pr, Pc);
-        SLU_REQUIRE(vstate == 2, "solve_block: the device storage holds no factors (factor first)");
+    // the same rules in the words of the block sweep's callers
+    void require_1x1_factors_block(const char *what = "solve_block") {
+        SLU_REQUIRE(!zmode, "%s: not on 3D plans (the block sweep runs on 1x1 plans only)", what);
+        SLU_REQUIRE(!xmode, "%s: not on a %dx%d grid (the block sweep has no exchanges; "
+                    "1x1 plans only)", what, Pr, Pc);
+        SLU_REQUIRE(vstate == 2, "%s: the device storage holds no factors (factor first)", what);
     }
 
     // ---- 2D grids: the distributed supernodal solve of pdgstrs
@@ -3841,17 +3850,18 @@ struct Plan : PlanBase {
         if (trans != SLU_NOTRANS) require_1x1_factors("solve_t");
         solve_op(trans, b, ldb, nrhs);
     }
-    // columns c0 .. c0 + nc of the host array b (ld ldb) to / from nc device
+    // columns c0 .. c0 + nc of the host array b (ld ldb, elements of E's
+    // size: T's, or doubles for the mixed-precision calls) to / from nc device
     // vectors of n values at dv, on `stream`
-    void cols_h2d(T *dv, const void *b, i64 ldb, int c0, int nc) {
+    template <typename E> void cols_h2d(E *dv, const void *b, i64 ldb, int c0, int nc) {
         for (int q = 0; q < nc; ++q)
-            HIPCHK(hipMemcpyAsync(dv + (i64)q * n, (const HT *)b + (i64)(c0 + q) * ldb, (size_t)n * sizeof(T),
-                                  hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(dv + (i64)q * n, (const char *)b + (i64)(c0 + q) * ldb * sizeof(E),
+                                  (size_t)n * sizeof(E), hipMemcpyHostToDevice, stream));
     }
-    void cols_d2h(void *b, i64 ldb, int c0, int nc, const T *dv) {
+    template <typename E> void cols_d2h(void *b, i64 ldb, int c0, int nc, const E *dv) {
         for (int q = 0; q < nc; ++q)
-            HIPCHK(hipMemcpyAsync((HT *)b + (i64)(c0 + q) * ldb, dv + (i64)q * n, (size_t)n * sizeof(T),
-                                  hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync((char *)b + (i64)(c0 + q) * ldb * sizeof(E), dv + (i64)q * n,
+                                  (size_t)n * sizeof(E), hipMemcpyDeviceToHost, stream));
     }
     void solve_op(int trans, void *b, int64_t ldb, int nrhs) {
         SLU_REQUIRE(!zmode, "solve: 3D plans hold the factors spread over the layers (gather them to a 2D plan)");
@@ -4214,6 +4224,153 @@ struct Plan : PlanBase {
                 [&](int j) { HIPCHK(hipMemcpyAsync(x + (i64)j * ld, d_d2_x.p, nb, hipMemcpyDeviceToHost, stream)); });
         } else {
             throw Error(fmt("refine_d2: fp32 plans only, this plan's dtype is %s", dtype_name()));
+        }
+    }
+
+    // ---- block refinement (refine_block.h): the loop of refine_loop on a
+    // pass of SvbNr columns at once.  X, B and R of the pass are row-major
+    // buffers of n rows of SvbNr values of E (T, or double on an fp32 plan's
+    // mixed-precision loop), three sections of d_rfb, allocated on first use
+    // and kept.  A host array's columns are staged through R, which holds
+    // nothing while a pass loads or stores.
+    DevBuf<char> d_rfb;
+    DevBuf<unsigned long long> d_rfb_max; // per column: bit patterns of berr, then (D2) of rmax
+
+    // Per column the rule of refine_loop: count / lstres / berr arrays, one
+    // D2H of the bit patterns per step, a stopped column frozen.
+    // step(xb, rb, act, live, mx) turns R into the correction of the columns
+    // of `act` and adds it to X (live = the pass's columns, mx = the
+    // residual's maxima).
+    template <typename E, bool D2, typename Cx>
+    void refine_block_loop(const char *what, const E *a, double eps, double safe1, double safe2, const void *b,
+                           void *x, i64 ld, int nrhs, int on_device, double *berr, int *steps, Cx step) {
+        constexpr int NRB = SvbNr<E>::v, NMAX = D2 ? 2 * NRB : NRB;
+        SLU_REQUIRE(ld >= n && nrhs >= 0, "%s: ld %lld < n %d or nrhs %d < 0", what, (long long)ld, n, nrhs);
+        rfb_passes = rfb_sweeps = rfb_resids = 0;
+        rfb_ms = 0;
+        stats.t_refine_ms = 0;
+        if (nrhs == 0 || n == 0) return;
+        if (!sv_ready) build_solve();
+        const size_t sec = (size_t)n * NRB * sizeof(E);
+        if (d_rfb.n < 3 * sec) d_rfb.alloc(3 * sec);
+        if (d_rfb_max.n < (size_t)NMAX) d_rfb_max.alloc(NMAX);
+        E *xb = (E *)d_rfb.p, *bb = (E *)(d_rfb.p + sec), *rb = (E *)(d_rfb.p + 2 * sec);
+        const unsigned tb = (unsigned)((n + SVB_TR_ROWS - 1) / SVB_TR_ROWS);
+        const unsigned rg = (unsigned)((n + RFB_THREADS / NRB - 1) / (RFB_THREADS / NRB));
+        EventTimer tm;
+        HIPCHK(hipStreamSynchronize(pstream));
+        tm.start(stream);
+        for (int r0 = 0; r0 < nrhs; r0 += NRB) {
+            const int nr = std::min(NRB, nrhs - r0);
+            const i64 ldc = on_device ? ld : (i64)n;
+            // b, then x: column-major on the device (the caller's, or staged in R) -> row-major
+            for (int w = 0; w < 2; ++w) {
+                const E *cols = on_device ? (const E *)(w ? x : b) + (i64)r0 * ld : rb;
+                if (!on_device) cols_h2d(rb, w ? x : b, ld, r0, nr);
+                hipLaunchKernelGGL((k_svb_in<E>), dim3(tb), dim3(256), 0, stream, cols, ldc, n, nr, w ? xb : bb);
+            }
+            const unsigned live = nr == 32 ? ~0u : (1u << nr) - 1;
+            unsigned act = live;
+            int count[NRB] = {};
+            double lstres[NRB], be[NRB] = {}, mx[NMAX];
+            std::fill(lstres, lstres + NRB, 3.0);
+            while (true) {
+                unsigned long long bits[NMAX];
+                HIPCHK(hipMemsetAsync(d_rfb_max.p, 0, sizeof bits, stream));
+                hipLaunchKernelGGL((k_rfb_resid<E, D2>), dim3(rg), dim3(RFB_THREADS), 0, stream, d_rp.p, d_rc.p,
+                                   d_re.p, a, (const E *)xb, (const E *)bb, rb, n, safe1, safe2, d_rfb_max.p);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(bits, d_rfb_max.p, sizeof bits, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                ++rfb_resids;
+                memcpy(mx, bits, sizeof bits);
+                unsigned go = 0;
+                for (int q = 0; q < nr; ++q) {
+                    if (!((act >> q) & 1u)) continue;
+                    be[q] = mx[q];
+                    if (be[q] > eps && be[q] * 2 <= lstres[q] && count[q] < 20) go |= 1u << q;
+                }
+                act = go;
+                if (!act) break;
+                step(xb, rb, act, live, mx);
+                HIPCHK(hipGetLastError());
+                for (int q = 0; q < nr; ++q) {
+                    if (!((act >> q) & 1u)) continue;
+                    lstres[q] = be[q];
+                    ++count[q];
+                }
+                ++rfb_sweeps;
+            }
+            E *cols = on_device ? (E *)x + (i64)r0 * ld : rb;
+            hipLaunchKernelGGL((k_svb_out<E>), dim3(tb), dim3(256), 0, stream, (const E *)xb, n, nr, cols, ldc);
+            HIPCHK(hipGetLastError());
+            if (!on_device) cols_d2h(x, ld, r0, nr, (const E *)rb);
+            HIPCHK(hipStreamSynchronize(stream));
+            for (int q = 0; q < nr; ++q) {
+                if (berr) berr[r0 + q] = be[q];
+                if (steps) steps[r0 + q] = count[q];
+            }
+            ++rfb_passes;
+        }
+        tm.stop(stream);
+        rfb_ms = stats.t_refine_ms = tm.ms();
+    }
+
+    void refine_block(const void *b, void *x, int64_t ld, int nrhs, int on_device, double *berr,
+                      int *steps) override {
+        require_1x1_factors_block("refine_block");
+        SLU_REQUIRE(a_fact != nullptr,
+                    "refine_block needs the values of A the factors came from (slu_plan_fill_a "
+                    "before slu_plan_factor)");
+        const bool dbl = !std::is_same<T, float>::value;
+        const double eps = dbl ? 0.5 * 2.220446049250313e-16 : 0.5 * 1.1920928955078125e-07;
+        const double safmin = dbl ? 2.2250738585072014e-308 : 1.1754943508222875e-38;
+        const double safe1 = (double)(n + 1) * safmin, safe2 = safe1 / eps;
+        const i64 total = (i64)n * SvbNr<T>::v;
+        const unsigned eb = (unsigned)((total + RFB_THREADS - 1) / RFB_THREADS);
+        refine_block_loop<T, false>(
+            "refine_block", a_fact, eps, safe1, safe2, b, x, ld, nrhs, on_device, berr, steps,
+            [&](T *xb, T *rb, unsigned act, unsigned live, const double *) {
+                if (act != live)
+                    hipLaunchKernelGGL(k_rfb_mask<T>, dim3(eb), dim3(RFB_THREADS), 0, stream, rb, total, act);
+                sweep_block(rb);
+                hipLaunchKernelGGL(k_rfb_axpy<T>, dim3(eb), dim3(RFB_THREADS), 0, stream, xb,
+                                   (const T *)rb, total, act);
+            });
+    }
+
+    // the block loop with refine_d2's step: per column rmax = m 2^e, the fp32
+    // block sweep of (float)(r 2^-e) in d_svb_x, x += 2^e dx in fp64
+    void refine_block_d2(const double *b, double *x, int64_t ld, int nrhs, int on_device, double *berr,
+                         int *steps) override {
+        require_1x1_factors_block("refine_block_d2");
+        if constexpr (std::is_same<T, float>::value) {
+            SLU_REQUIRE(a_fact64 != nullptr,
+                        "refine_block_d2 needs the fp64 values of A the factors came from "
+                        "(slu_plan_fill_a_d2 before slu_plan_factor)");
+            constexpr int NRB = SvbNr<float>::v;
+            const double eps = 0.5 * 2.220446049250313e-16, safmin = 2.2250738585072014e-308;
+            const double safe1 = (double)(n + 1) * safmin, safe2 = safe1 / eps;
+            const i64 total = (i64)n * NRB;
+            const unsigned eb = (unsigned)((total + RFB_THREADS - 1) / RFB_THREADS);
+            if (ld >= n && nrhs > 0 && d_svb_x.n < (size_t)total) d_svb_x.alloc((size_t)total);
+            refine_block_loop<double, true>(
+                "refine_block_d2", a_fact64, eps, safe1, safe2, b, x, ld, nrhs, on_device, berr, steps,
+                [&](double *xb, double *rb, unsigned act, unsigned, const double *mx) {
+                    RfbExp ex;
+                    for (int q = 0; q < NRB; ++q) {
+                        const double rmax = mx[NRB + q];
+                        ex.e[q] = 0;
+                        if (rmax > 0.0 && std::isfinite(rmax)) (void)frexp(rmax, &ex.e[q]);
+                    }
+                    hipLaunchKernelGGL(k_rfb_scale_cvt_d2, dim3(eb), dim3(RFB_THREADS), 0, stream,
+                                       (const double *)rb, d_svb_x.p, total, ex, act);
+                    sweep_block(d_svb_x.p);
+                    hipLaunchKernelGGL(k_rfb_axpy_d2, dim3(eb), dim3(RFB_THREADS), 0, stream, xb,
+                                       (const float *)d_svb_x.p, total, ex, act);
+                });
+        } else {
+            throw Error(fmt("refine_block_d2: fp32 plans only, this plan's dtype is %s", dtype_name()));
         }
     }
 
@@ -4837,6 +4994,28 @@ int slu_plan_refine_d2(slu_plan *p, const double *b, double *x, int64_t ld, int 
     return guarded([&] {
         p->impl->refine_d2(b, x, ld, nrhs, berr, steps);
     });
+}
+
+int slu_plan_refine_block(slu_plan *p, const void *b, void *x, int64_t ld, int nrhs, int on_device,
+                          double *berr, int *steps) {
+    return guarded([&] {
+        p->impl->refine_block(b, x, ld, nrhs, on_device, berr, steps);
+    });
+}
+
+int slu_plan_refine_block_d2(slu_plan *p, const double *b, double *x, int64_t ld, int nrhs, int on_device,
+                             double *berr, int *steps) {
+    return guarded([&] {
+        p->impl->refine_block_d2(b, x, ld, nrhs, on_device, berr, steps);
+    });
+}
+
+int slu_plan_refine_block_info(const slu_plan *p, int *passes, int *sweeps, int *resids, double *ms) {
+    if (passes) *passes = p->impl->rfb_passes;
+    if (sweeps) *sweeps = p->impl->rfb_sweeps;
+    if (resids) *resids = p->impl->rfb_resids;
+    if (ms) *ms = p->impl->rfb_ms;
+    return 0;
 }
 
 int slu_plan_download(slu_plan *p) {

@@ -127,6 +127,23 @@ struct CoarsePlan : PlanBase {
         in->refine_d2(b, x, ld, nrhs, berr, steps);
         sync_stats();
     }
+    void sync_rfb() {
+        rfb_passes = in->rfb_passes;
+        rfb_sweeps = in->rfb_sweeps;
+        rfb_resids = in->rfb_resids;
+        rfb_ms = in->rfb_ms;
+        sync_stats();
+    }
+    void refine_block(const void *b, void *x, int64_t ld, int nrhs, int on_device, double *berr,
+                      int *steps) override {
+        in->refine_block(b, x, ld, nrhs, on_device, berr, steps);
+        sync_rfb();
+    }
+    void refine_block_d2(const double *b, double *x, int64_t ld, int nrhs, int on_device, double *berr,
+                         int *steps) override {
+        in->refine_block_d2(b, x, ld, nrhs, on_device, berr, steps);
+        sync_rfb();
+    }
     void check_exchange(int64_t *nsec, int64_t *nbytes) override {
         in->check_exchange(nsec, nbytes);
         sync_stats();

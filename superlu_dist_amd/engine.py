@@ -318,6 +318,54 @@ class Plan:
                                            steps.ctypes.data_as(C.POINTER(C.c_int))))
         return xx, berr[:nrhs], steps[:nrhs]
 
+    def _refine_block(self, b, x, d2):
+        dt = np.float64 if d2 else self.lu.Lval.dtype
+        bb = np.array(b, dtype=dt, order="F", copy=True)
+        xx = np.array(x, dtype=dt, order="F", copy=True)
+        if bb.shape != xx.shape:
+            raise ValueError("b and x differ in shape")
+        nrhs = 1 if bb.ndim == 1 else bb.shape[1]
+        berr = np.zeros(max(nrhs, 1))
+        steps = np.zeros(max(nrhs, 1), dtype=np.int32)
+        fn = lib().slu_plan_refine_block_d2 if d2 else lib().slu_plan_refine_block
+        self._chk(fn(self.ptr, bb.ctypes.data_as(C.c_void_p), xx.ctypes.data_as(C.c_void_p),
+                     bb.shape[0], nrhs, 0, berr.ctypes.data_as(C.POINTER(C.c_double)),
+                     steps.ctypes.data_as(C.POINTER(C.c_int))))
+        return xx, berr[:nrhs], steps[:nrhs]
+
+    def refine_block(self, b, x):
+        """refine() on a block of right-hand sides (1x1 plans): 32 columns per
+        pass (16 complex) share each step's residual kernel and block sweep,
+        every column with its own stopping rule; a column that has stopped is
+        not changed by its neighbours' later steps.  b, x: (n,) or (n, nrhs).
+        Returns (x, berr, steps) per column, as refine()."""
+        return self._refine_block(b, x, False)
+
+    def refine_block_d2(self, b, x):
+        """refine_d2() on a block of right-hand sides (fp32 1x1 plans after
+        fill_a_d2): b, x float64, every column with its own power-of-two
+        normalisation.  Returns (x, berr, steps) per column, as refine_d2()."""
+        return self._refine_block(b, x, True)
+
+    def refine_block_dev(self, bptr, xptr, ld, nrhs, d2=False):
+        """refine_block (d2: refine_block_d2) on column-major device arrays
+        (raw pointers, leading dimension ld >= n, the plan's element type or
+        float64 with d2); x is refined in place, b is not written.  Returns
+        (berr, steps) per column after the device finished."""
+        berr = np.zeros(max(nrhs, 1))
+        steps = np.zeros(max(nrhs, 1), dtype=np.int32)
+        fn = lib().slu_plan_refine_block_d2 if d2 else lib().slu_plan_refine_block
+        self._chk(fn(self.ptr, C.c_void_p(int(bptr)), C.c_void_p(int(xptr)), int(ld), int(nrhs), 1,
+                     berr.ctypes.data_as(C.POINTER(C.c_double)), steps.ctypes.data_as(C.POINTER(C.c_int))))
+        return berr[:nrhs], steps[:nrhs]
+
+    def refine_block_info(self):
+        """(passes, block sweeps, residual launches, device ms) of the last
+        refine_block / refine_block_d2."""
+        k, ns, nr, ms = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        lib().slu_plan_refine_block_info(self.ptr, C.byref(k), C.byref(ns), C.byref(nr), C.byref(ms))
+        return k.value, ns.value, nr.value, ms.value
+
     def check_exchange(self):
         """Schedule-only plans: replay every level's exchange phases of
         factor() through the communicator, each received section checked
