@@ -347,6 +347,32 @@ int slu_plan_refine_block(slu_plan *p, const void *b, void *x, int64_t ld, int n
 int slu_plan_refine_block_d2(slu_plan *p, const double *b, double *x, int64_t ld, int nrhs,
                              int on_device, double *berr, int *steps);
 int slu_plan_refine_block_info(const slu_plan *p, int *passes, int *sweeps, int *resids, double *ms);
+/* slu_plan_solve_block / slu_plan_refine_block with the transpose (1x1
+ * plans): op(B)^T X = C for SVB_NR columns per pass on the same factors,
+ * tables, levels and working buffers, with no storage beyond them
+ * (csrc/solve_block_t.h).  trans as in slu_plan_solve_t: SLU_NOTRANS runs
+ * exactly slu_plan_solve_block / slu_plan_refine_block, SLU_TRANS B^T,
+ * SLU_CONJ B^H (on a real plan the same as SLU_TRANS); any other value is
+ * refused.  U^T Z = C runs forward (U's row segments pushed), L^T Y = Z
+ * backward (L's panels pulled); in both panel products and in both diagonal
+ * solves the MFMA K index runs along the stored contiguous dimension of the
+ * factor.  b, x, ld, nrhs, on_device, what is written and what is not, the
+ * staging of host arrays and the working buffers: as in the untransposed
+ * calls.  A zero pivot yields non-finite columns, as slu_plan_solve_t.
+ * refine_block_t: per column the semantics of slu_plan_refine_t
+ * (r = c - op(B)^T x, s = |B^T||x| + |c| over the CSC of
+ * slu_plan_set_a_pattern, same eps, safmin, SAFE1/SAFE2 guards, at most 20
+ * steps, NaN wins the max) with the frozen-column contract of
+ * slu_plan_refine_block.  It needs the A of slu_plan_fill_a and refuses
+ * factors of a slu_plan_fill_a_d2 (there is no transposed mixed-precision
+ * block loop).  berr and steps may be NULL.
+ * slu_plan_solve_block_info / slu_plan_refine_block_info report the last call
+ * of either kind, t_solve_ms / t_refine_ms likewise.  Nothing dispatches here
+ * automatically: below one pass's worth of columns slu_plan_solve_t is the
+ * faster call. */
+int slu_plan_solve_block_t(slu_plan *p, int trans, void *b, int64_t ldb, int nrhs, int on_device);
+int slu_plan_refine_block_t(slu_plan *p, int trans, const void *b, void *x, int64_t ld, int nrhs,
+                            int on_device, double *berr, int *steps);
 /* Schedule-only plans: replay every level's exchange phases of
  * slu_plan_factor through the communicator on host buffers; each received
  * section is checked byte for byte against what its root wrote.  Collective;

@@ -49,6 +49,7 @@
 #include "fill.h"
 #include "solve.h"
 #include "solve_block.h"
+#include "solve_block_t.h"
 #include "refine_d2.h"
 #include "refine_block.h"
 #include "hostio.h"
@@ -350,6 +351,10 @@ struct PlanBase {
                                  int *steps) = 0;
     int rfb_passes = 0, rfb_sweeps = 0, rfb_resids = 0;
     double rfb_ms = 0;
+    // solve_block / refine_block with B^T / B^H (solve_block_t.h); svb_* and rfb_* as above
+    virtual void solve_block_t(int trans, void *b, int64_t ldb, int nrhs, int on_device) = 0;
+    virtual void refine_block_t(int trans, const void *b, void *x, int64_t ld, int nrhs, int on_device,
+                                double *berr, int *steps) = 0;
     virtual void check_exchange(int64_t *nsec, int64_t *nbytes) = 0;
     virtual void gather_layers() { throw Error("gather_layers: not a 3D plan"); }
     virtual void adopt_factors() = 0; // upload host values that are already factors
@@ -3905,9 +3910,37 @@ struct Plan : PlanBase {
         HIPCHK(hipGetLastError());
         return nk;
     }
+    // the transposed block sweep (solve_block_t.h): the level walk of
+    // sweep_t_nr on the row-major X; returns the launches
+    i64 sweep_block_t(T *xb, int conj) {
+        const int nl = (int)bylev.size();
+        i64 nk = 0;
+        for (int L = 0; L < nl; ++L) { // U^T Z = C
+            nk += sv_diag(L, k_svb_utdiag<T>, SVB_DTHREADS, xb, conj);
+            nk += sv_upan(L, k_svb_utpanel<T>, SV_THREADS, xb, conj);
+        }
+        for (int L = nl - 1; L >= 0; --L) { // L^T Y = Z
+            nk += sv_lpan(L, k_svb_ltpanel<T>, SVB_LTHREADS, xb, conj);
+            nk += sv_diag(L, k_svb_ltdiag<T>, SVB_DTHREADS, xb, conj);
+        }
+        HIPCHK(hipGetLastError());
+        return nk;
+    }
+    // op(B)^-1 on the row-major X: trans 0 = B, 1 = B^T, 2 = B^H
+    i64 sweep_block_op(int trans, T *xb) {
+        return trans ? sweep_block_t(xb, trans == SLU_CONJ) : sweep_block(xb);
+    }
     void solve_block(void *b, int64_t ldb, int nrhs, int on_device) override {
-        require_1x1_factors_block();
-        SLU_REQUIRE(ldb >= n && nrhs >= 0, "solve_block: ldb %lld < n %d or nrhs %d < 0", (long long)ldb, n, nrhs);
+        solve_block_op("solve_block", SLU_NOTRANS, b, ldb, nrhs, on_device);
+    }
+    void solve_block_t(int trans, void *b, int64_t ldb, int nrhs, int on_device) override {
+        SLU_REQUIRE(trans >= SLU_NOTRANS && trans <= SLU_CONJ,
+                    "solve_block_t: trans = %d is none of SLU_NOTRANS, SLU_TRANS, SLU_CONJ", trans);
+        solve_block_op(trans ? "solve_block_t" : "solve_block", trans, b, ldb, nrhs, on_device);
+    }
+    void solve_block_op(const char *what, int trans, void *b, int64_t ldb, int nrhs, int on_device) {
+        require_1x1_factors_block(what);
+        SLU_REQUIRE(ldb >= n && nrhs >= 0, "%s: ldb %lld < n %d or nrhs %d < 0", what, (long long)ldb, n, nrhs);
         svb_passes = 0;
         svb_launches = 0;
         svb_ms = 0;
@@ -3928,7 +3961,7 @@ struct Plan : PlanBase {
             if (!on_device) cols_h2d(cols, b, ldb, r0, nr);
             tm.start(stream);
             hipLaunchKernelGGL((k_svb_in<T>), dim3(tb), dim3(256), 0, stream, (const T *)cols, ldc, n, nr, d_svb_x.p);
-            svb_launches += 2 + sweep_block(d_svb_x.p);
+            svb_launches += 2 + sweep_block_op(trans, d_svb_x.p);
             hipLaunchKernelGGL((k_svb_out<T>), dim3(tb), dim3(256), 0, stream, (const T *)d_svb_x.p, n, nr, cols, ldc);
             HIPCHK(hipGetLastError());
             tm.stop(stream);
@@ -4238,12 +4271,13 @@ struct Plan : PlanBase {
 
     // Per column the rule of refine_loop: count / lstres / berr arrays, one
     // D2H of the bit patterns per step, a stopped column frozen.
-    // step(xb, rb, act, live, mx) turns R into the correction of the columns
-    // of `act` and adds it to X (live = the pass's columns, mx = the
-    // residual's maxima).
-    template <typename E, bool D2, typename Cx>
-    void refine_block_loop(const char *what, const E *a, double eps, double safe1, double safe2, const void *b,
-                           void *x, i64 ld, int nrhs, int on_device, double *berr, int *steps, Cx step) {
+    // resid(xb, bb, rb, rg, out) launches the residual kernel of the pass on
+    // rg workgroups (R and the per-column maxima `out`); step(xb, rb, act,
+    // live, mx) turns R into the correction of the columns of `act` and adds
+    // it to X (live = the pass's columns, mx = the residual's maxima).
+    template <typename E, bool D2, typename Rs, typename Cx>
+    void refine_block_loop(const char *what, double eps, const void *b, void *x, i64 ld, int nrhs, int on_device,
+                           double *berr, int *steps, Rs resid, Cx step) {
         constexpr int NRB = SvbNr<E>::v, NMAX = D2 ? 2 * NRB : NRB;
         SLU_REQUIRE(ld >= n && nrhs >= 0, "%s: ld %lld < n %d or nrhs %d < 0", what, (long long)ld, n, nrhs);
         rfb_passes = rfb_sweeps = rfb_resids = 0;
@@ -4277,8 +4311,7 @@ struct Plan : PlanBase {
             while (true) {
                 unsigned long long bits[NMAX];
                 HIPCHK(hipMemsetAsync(d_rfb_max.p, 0, sizeof bits, stream));
-                hipLaunchKernelGGL((k_rfb_resid<E, D2>), dim3(rg), dim3(RFB_THREADS), 0, stream, d_rp.p, d_rc.p,
-                                   d_re.p, a, (const E *)xb, (const E *)bb, rb, n, safe1, safe2, d_rfb_max.p);
+                resid((const E *)xb, (const E *)bb, rb, rg, d_rfb_max.p);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipMemcpyAsync(bits, d_rfb_max.p, sizeof bits, hipMemcpyDeviceToHost, stream));
                 HIPCHK(hipStreamSynchronize(stream));
@@ -4316,27 +4349,58 @@ struct Plan : PlanBase {
         rfb_ms = stats.t_refine_ms = tm.ms();
     }
 
+    // the untransposed residual of a pass: k_rfb_resid over the rows of A
+    template <typename E, bool D2> auto rfb_resid_rows(const E *a, double safe1, double safe2) {
+        return [=](const E *xb, const E *bb, E *rb, unsigned rg, unsigned long long *out) {
+            hipLaunchKernelGGL((k_rfb_resid<E, D2>), dim3(rg), dim3(RFB_THREADS), 0, stream, d_rp.p, d_rc.p,
+                               d_re.p, a, xb, bb, rb, n, safe1, safe2, out);
+        };
+    }
+
     void refine_block(const void *b, void *x, int64_t ld, int nrhs, int on_device, double *berr,
                       int *steps) override {
-        require_1x1_factors_block("refine_block");
+        refine_block_op("refine_block", SLU_NOTRANS, b, x, ld, nrhs, on_device, berr, steps);
+    }
+    void refine_block_t(int trans, const void *b, void *x, int64_t ld, int nrhs, int on_device, double *berr,
+                        int *steps) override {
+        SLU_REQUIRE(trans >= SLU_NOTRANS && trans <= SLU_CONJ,
+                    "refine_block_t: trans = %d is none of SLU_NOTRANS, SLU_TRANS, SLU_CONJ", trans);
+        refine_block_op(trans ? "refine_block_t" : "refine_block", trans, b, x, ld, nrhs, on_device, berr, steps);
+    }
+    // trans != 0: the residual by columns of A (k_rfb_resid_t over build_csc's
+    // view) and the transposed block sweep, the rest of the loop unchanged
+    void refine_block_op(const char *what, int trans, const void *b, void *x, int64_t ld, int nrhs, int on_device,
+                         double *berr, int *steps) {
+        require_1x1_factors_block(what);
         SLU_REQUIRE(a_fact != nullptr,
-                    "refine_block needs the values of A the factors came from (slu_plan_fill_a "
-                    "before slu_plan_factor)");
+                    "%s needs the values of A the factors came from (slu_plan_fill_a "
+                    "before slu_plan_factor)", what);
         const bool dbl = !std::is_same<T, float>::value;
         const double eps = dbl ? 0.5 * 2.220446049250313e-16 : 0.5 * 1.1920928955078125e-07;
         const double safmin = dbl ? 2.2250738585072014e-308 : 1.1754943508222875e-38;
         const double safe1 = (double)(n + 1) * safmin, safe2 = safe1 / eps;
         const i64 total = (i64)n * SvbNr<T>::v;
         const unsigned eb = (unsigned)((total + RFB_THREADS - 1) / RFB_THREADS);
+        const int conj = trans == SLU_CONJ;
+        auto step = [&](T *xb, T *rb, unsigned act, unsigned live, const double *) {
+            if (act != live)
+                hipLaunchKernelGGL(k_rfb_mask<T>, dim3(eb), dim3(RFB_THREADS), 0, stream, rb, total, act);
+            sweep_block_op(trans, rb);
+            hipLaunchKernelGGL(k_rfb_axpy<T>, dim3(eb), dim3(RFB_THREADS), 0, stream, xb, (const T *)rb, total, act);
+        };
+        if (!trans) {
+            refine_block_loop<T, false>(what, eps, b, x, ld, nrhs, on_device, berr, steps,
+                                        rfb_resid_rows<T, false>(a_fact, safe1, safe2), step);
+            return;
+        }
+        if (ld >= n && nrhs > 0 && n > 0 && !csc_ready) build_csc();
         refine_block_loop<T, false>(
-            "refine_block", a_fact, eps, safe1, safe2, b, x, ld, nrhs, on_device, berr, steps,
-            [&](T *xb, T *rb, unsigned act, unsigned live, const double *) {
-                if (act != live)
-                    hipLaunchKernelGGL(k_rfb_mask<T>, dim3(eb), dim3(RFB_THREADS), 0, stream, rb, total, act);
-                sweep_block(rb);
-                hipLaunchKernelGGL(k_rfb_axpy<T>, dim3(eb), dim3(RFB_THREADS), 0, stream, xb,
-                                   (const T *)rb, total, act);
-            });
+            what, eps, b, x, ld, nrhs, on_device, berr, steps,
+            [&](const T *xb, const T *bb, T *rb, unsigned rg, unsigned long long *out) {
+                hipLaunchKernelGGL(k_rfb_resid_t<T>, dim3(rg), dim3(RFB_THREADS), 0, stream, d_csc_lo.p, d_csc_hi.p,
+                                   d_csc_ci.p, a_fact, xb, bb, rb, n, safe1, safe2, out, conj);
+            },
+            step);
     }
 
     // the block loop with refine_d2's step: per column rmax = m 2^e, the fp32
@@ -4355,7 +4419,8 @@ struct Plan : PlanBase {
             const unsigned eb = (unsigned)((total + RFB_THREADS - 1) / RFB_THREADS);
             if (ld >= n && nrhs > 0 && d_svb_x.n < (size_t)total) d_svb_x.alloc((size_t)total);
             refine_block_loop<double, true>(
-                "refine_block_d2", a_fact64, eps, safe1, safe2, b, x, ld, nrhs, on_device, berr, steps,
+                "refine_block_d2", eps, b, x, ld, nrhs, on_device, berr, steps,
+                rfb_resid_rows<double, true>(a_fact64, safe1, safe2),
                 [&](double *xb, double *rb, unsigned act, unsigned, const double *mx) {
                     RfbExp ex;
                     for (int q = 0; q < NRB; ++q) {
@@ -5007,6 +5072,19 @@ int slu_plan_refine_block_d2(slu_plan *p, const double *b, double *x, int64_t ld
                              double *berr, int *steps) {
     return guarded([&] {
         p->impl->refine_block_d2(b, x, ld, nrhs, on_device, berr, steps);
+    });
+}
+
+int slu_plan_solve_block_t(slu_plan *p, int trans, void *b, int64_t ldb, int nrhs, int on_device) {
+    return guarded([&] {
+        p->impl->solve_block_t(trans, b, ldb, nrhs, on_device);
+    });
+}
+
+int slu_plan_refine_block_t(slu_plan *p, int trans, const void *b, void *x, int64_t ld, int nrhs,
+                            int on_device, double *berr, int *steps) {
+    return guarded([&] {
+        p->impl->refine_block_t(trans, b, x, ld, nrhs, on_device, berr, steps);
     });
 }
 

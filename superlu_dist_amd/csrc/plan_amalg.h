@@ -85,12 +85,19 @@ struct CoarsePlan : PlanBase {
         in->solve(b, ldb, nrhs);
         sync_stats();
     }
-    void solve_block(void *b, int64_t ldb, int nrhs, int on_device) override {
-        in->solve_block(b, ldb, nrhs, on_device);
+    void sync_svb() {
         svb_passes = in->svb_passes;
         svb_launches = in->svb_launches;
         svb_ms = in->svb_ms;
         sync_stats();
+    }
+    void solve_block(void *b, int64_t ldb, int nrhs, int on_device) override {
+        in->solve_block(b, ldb, nrhs, on_device);
+        sync_svb();
+    }
+    void solve_block_t(int trans, void *b, int64_t ldb, int nrhs, int on_device) override {
+        in->solve_block_t(trans, b, ldb, nrhs, on_device);
+        sync_svb();
     }
     void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) override {
         in->set_a_pattern(ncol, xa, asub);
@@ -137,6 +144,11 @@ struct CoarsePlan : PlanBase {
     void refine_block(const void *b, void *x, int64_t ld, int nrhs, int on_device, double *berr,
                       int *steps) override {
         in->refine_block(b, x, ld, nrhs, on_device, berr, steps);
+        sync_rfb();
+    }
+    void refine_block_t(int trans, const void *b, void *x, int64_t ld, int nrhs, int on_device, double *berr,
+                        int *steps) override {
+        in->refine_block_t(trans, b, x, ld, nrhs, on_device, berr, steps);
         sync_rfb();
     }
     void refine_block_d2(const double *b, double *x, int64_t ld, int nrhs, int on_device, double *berr,

@@ -215,24 +215,30 @@ class Plan:
                                              x.ctypes.data_as(C.c_void_p), n, nrhs))
         return x
 
-    def solve_block(self, b):
+    def _solve_block(self, trans, ptr, ldb, nrhs, on_device):
+        if trans == "N":
+            self._chk(lib().slu_plan_solve_block(self.ptr, ptr, ldb, nrhs, on_device))
+        else:
+            self._chk(lib().slu_plan_solve_block_t(self.ptr, self._trans(trans), ptr, ldb, nrhs, on_device))
+
+    def solve_block(self, b, trans="N"):
         """Solve L U X = B for a block of right-hand sides: every factor
         element is read once per sweep for 32 columns (16 complex), the panel
         products on MFMA (1x1 plans).  b: (n,) or (n, nrhs).  Returns x as
         solve() does; the caller chooses between the two (solve() is the
-        faster one for a few columns)."""
+        faster one for a few columns).  trans="T" / "C": with the transpose /
+        conjugate transpose of the factored matrix, as solve()."""
         dt = self.lu.Lval.dtype
         x = np.array(b, dtype=dt, order="F", copy=True)
         nrhs = 1 if x.ndim == 1 else x.shape[1]
-        self._chk(lib().slu_plan_solve_block(self.ptr, x.ctypes.data_as(C.c_void_p),
-                                             x.shape[0], nrhs, 0))
+        self._solve_block(trans, x.ctypes.data_as(C.c_void_p), x.shape[0], nrhs, 0)
         return x
 
-    def solve_block_dev(self, ptr, ldb, nrhs):
+    def solve_block_dev(self, ptr, ldb, nrhs, trans="N"):
         """solve_block in place on a column-major device array (raw pointer,
         leading dimension ldb >= n, the plan's element type); returns after
         the device finished."""
-        self._chk(lib().slu_plan_solve_block(self.ptr, C.c_void_p(int(ptr)), int(ldb), int(nrhs), 1))
+        self._solve_block(trans, C.c_void_p(int(ptr)), int(ldb), int(nrhs), 1)
 
     def solve_block_info(self):
         """(passes over the factors, kernel launches, device ms) of the last solve_block."""
@@ -318,7 +324,16 @@ class Plan:
                                            steps.ctypes.data_as(C.POINTER(C.c_int))))
         return xx, berr[:nrhs], steps[:nrhs]
 
-    def _refine_block(self, b, x, d2):
+    def _refine_block_fn(self, d2, trans):
+        """the C entry of refine_block / refine_block_d2, or refine_block_t bound to trans"""
+        if trans == "N":
+            return lib().slu_plan_refine_block_d2 if d2 else lib().slu_plan_refine_block
+        if d2:
+            raise ValueError("refine_block_d2 has no transposed loop (d2=True needs trans='N')")
+        code = self._trans(trans)
+        return lambda ptr, *args: lib().slu_plan_refine_block_t(ptr, code, *args)
+
+    def _refine_block(self, b, x, d2, trans="N"):
         dt = np.float64 if d2 else self.lu.Lval.dtype
         bb = np.array(b, dtype=dt, order="F", copy=True)
         xx = np.array(x, dtype=dt, order="F", copy=True)
@@ -327,19 +342,20 @@ class Plan:
         nrhs = 1 if bb.ndim == 1 else bb.shape[1]
         berr = np.zeros(max(nrhs, 1))
         steps = np.zeros(max(nrhs, 1), dtype=np.int32)
-        fn = lib().slu_plan_refine_block_d2 if d2 else lib().slu_plan_refine_block
+        fn = self._refine_block_fn(d2, trans)
         self._chk(fn(self.ptr, bb.ctypes.data_as(C.c_void_p), xx.ctypes.data_as(C.c_void_p),
                      bb.shape[0], nrhs, 0, berr.ctypes.data_as(C.POINTER(C.c_double)),
                      steps.ctypes.data_as(C.POINTER(C.c_int))))
         return xx, berr[:nrhs], steps[:nrhs]
 
-    def refine_block(self, b, x):
+    def refine_block(self, b, x, trans="N"):
         """refine() on a block of right-hand sides (1x1 plans): 32 columns per
         pass (16 complex) share each step's residual kernel and block sweep,
         every column with its own stopping rule; a column that has stopped is
         not changed by its neighbours' later steps.  b, x: (n,) or (n, nrhs).
-        Returns (x, berr, steps) per column, as refine()."""
-        return self._refine_block(b, x, False)
+        Returns (x, berr, steps) per column, as refine().  trans="T" / "C":
+        for A^T x = b / A^H x = b, as refine()."""
+        return self._refine_block(b, x, False, trans)
 
     def refine_block_d2(self, b, x):
         """refine_d2() on a block of right-hand sides (fp32 1x1 plans after
@@ -347,14 +363,15 @@ class Plan:
         normalisation.  Returns (x, berr, steps) per column, as refine_d2()."""
         return self._refine_block(b, x, True)
 
-    def refine_block_dev(self, bptr, xptr, ld, nrhs, d2=False):
+    def refine_block_dev(self, bptr, xptr, ld, nrhs, d2=False, trans="N"):
         """refine_block (d2: refine_block_d2) on column-major device arrays
         (raw pointers, leading dimension ld >= n, the plan's element type or
         float64 with d2); x is refined in place, b is not written.  Returns
-        (berr, steps) per column after the device finished."""
+        (berr, steps) per column after the device finished.  trans as in
+        refine_block (not with d2)."""
         berr = np.zeros(max(nrhs, 1))
         steps = np.zeros(max(nrhs, 1), dtype=np.int32)
-        fn = lib().slu_plan_refine_block_d2 if d2 else lib().slu_plan_refine_block
+        fn = self._refine_block_fn(d2, trans)
         self._chk(fn(self.ptr, C.c_void_p(int(bptr)), C.c_void_p(int(xptr)), int(ld), int(nrhs), 1,
                      berr.ctypes.data_as(C.POINTER(C.c_double)), steps.ctypes.data_as(C.POINTER(C.c_int))))
         return berr[:nrhs], steps[:nrhs]

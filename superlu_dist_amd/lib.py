@@ -187,6 +187,9 @@ def lib():
         "slu_plan_refine_block_d2": (C.c_int, [P, P, P, C.c_int64, C.c_int, C.c_int,
                                                C.POINTER(C.c_double), c_intp]),
         "slu_plan_refine_block_info": (C.c_int, [P, c_intp, c_intp, c_intp, C.POINTER(C.c_double)]),
+        "slu_plan_solve_block_t": (C.c_int, [P, C.c_int, P, C.c_int64, C.c_int, C.c_int]),
+        "slu_plan_refine_block_t": (C.c_int, [P, C.c_int, P, P, C.c_int64, C.c_int, C.c_int,
+                                              C.POINTER(C.c_double), c_intp]),
         "slu_plan_snapshot": (C.c_int, [P]),
         "slu_plan_restore": (C.c_int, [P]),
         "slu_plan_sync": (C.c_int, [P]),
