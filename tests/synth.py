@@ -9,6 +9,10 @@ block meets (the engine dispatches on block widths, csrc/engine.hip) instead
 of taking whatever nested dissection of a stencil gives it.  ``pivot`` plants
 an exact pivot value at any column.
 
+``synth_sym`` builds structurally symmetric, nested matrices on arms of chained
+blocks, again with exactly the requested partition: the chains the engine's
+amalgamation merges (csrc/amalg.h), which ``synth``'s ragged U never does.
+
 ``dense_lu_ref`` is an unpivoted right-looking LU in ``np.longdouble`` with
 the tiny-pivot rule of oracle/oracle_impl.h; ``lu_to_dense`` scatters a
 factored 1x1 LUstruct into a dense matrix to compare with it; ``ld_solve``
@@ -55,11 +59,78 @@ FAMILIES = {
     "max_inner": _CHAIN([512, 200]),
     "max511_inner": _CHAIN([511, 150]),
 }
+# Families of synth_sym (structurally symmetric and nested: the engine's
+# amalgamation merges their chains; tests/test_synth.py pins every edge named
+# here by recomputing it from the LUstruct; tests/test_gpu_amalg_shapes.py).
+_U257 = [0] + [1] * 63 + [0, 1, 2, 3, 4] * 8   # a 5-wide block's U first rows: 5 + 63 x 4 = 257, then 5 .. 1
+SYM_FAMILIES = {
+    # one group of exactly 256 columns (FAST_MAXW); the 100-wide member's U
+    # row: ragged chunks of 3000 values and a last chunk of 4 columns
+    "amalg_w256": {"arms": [[100, 156]], "root": 64},
+    # 60 + 100 + 97 = 257: the greedy walk stops at 160 and starts again at
+    # the 97-wide block, which takes the 40-wide one
+    "amalg_w257": {"arms": [[60, 100, 97, 40]], "root": 64},
+    # merged groups of 61, 10 and 256 columns, an unmerged 20-wide block (20 +
+    # 300 > 256) and the 300-wide root: four groups in the first level.  L
+    # block columns of 257, 255 and 256 stored rows (the 4-, 16- and 56-wide
+    # blocks); 200 x 454 and 300 x 300 values: two k_amalg_l items each.  The
+    # keep makes the U chunks of the first level 35, not a multiple of 4
+    "amalg_mixed": {"arms": [[4, 16, 41], [20], {"widths": [1, 2, 7], "keep": -10}, [200, 56]], "root": 300},
+    # the U chunk edges of k_amalg_u.  [4, 67] "top": 129 = 2 x 64 + 1 columns
+    # of length 4, chunks of 256, 256 and 4 values, the second with one column
+    # in the coarse L and 63 in the coarse U.  [5, 40] with _U257: a chunk of
+    # 257 values over 38 columns of the coarse L and 26 of the coarse U, then
+    # 38 ragged columns on the short path.  [17, 30]: ragged on the long path,
+    # both kinds.  Nine width-1 blocks that merge with the root
+    "amalg_uchunk": {"arms": [{"widths": [4, 67], "ufirst": "top"}, {"widths": [5, 40], "ufirst": _U257},
+                              [17, 30], {"widths": [1] * 9, "drop": 0, "keep": -1}], "root": 96},
+    # no explicit zeros: a dense chain of 256 columns (drop = 0, "top") that the
+    # symbolic stage cuts at its supernode width limit, maxsup = 64, and the
+    # amalgamation joins again into one group of exactly FAST_MAXW columns in
+    # which every member row is present
+    "amalg_dense": {"arms": [{"widths": [64, 64, 64, 64], "drop": 0, "ufirst": "top"}], "root": 64, "maxsup": 64},
+    # the production shape: a chain of twelve width-1 supernodes, each
+    # without one row of its parent's, merged into one group
+    "amalg_ones": {"arms": [{"widths": [1] * 12, "drop": 0, "keep": -1}, [30, 40]], "root": 150},
+}
 MAXSUP = 512
 
 
 def offsets(blocks):
     return np.concatenate([[0], np.cumsum([w for w, _ in blocks])]).astype(np.int64)
+
+
+def _valued(P, rng, dtype, pivot):
+    """(Csc, dense matrix) with the pattern P: random values, a dominant
+    diagonal, planted pivots (synth's docstring)."""
+    n = P.shape[0]
+    npt = DTYPES[dtype]
+    V = rng.uniform(-1.0, 1.0, (n, n))
+    if dtype == SLU_Z:
+        V = V + 1j * rng.uniform(-1.0, 1.0, (n, n))
+    V = np.where(P, V, 0).astype(npt)
+    np.fill_diagonal(V, 0)
+    a = np.abs(V).astype(np.float64)
+    d = 1.05 * np.maximum(a.sum(axis=1), a.sum(axis=0)) + 1.0
+    if dtype == SLU_Z:
+        d = d * np.exp(2j * np.pi * rng.random(n))
+    else:
+        d = d * rng.choice([-1.0, 1.0], n)
+    V[np.arange(n), np.arange(n)] = d.astype(npt)
+    if pivot is not None:
+        pv = [pivot] if np.isscalar(pivot[0]) else list(pivot)
+        for col, val in pv:
+            V[col, :col] = 0      # stays in the pattern P: explicit stored zeros
+            V[col, col] = val
+    colptr = np.zeros(n + 1, dtype=np.int64)
+    ri, vv = [], []
+    for j in range(n):
+        r = np.nonzero(P[:, j])[0]
+        ri.append(r)
+        vv.append(V[r, j])
+        colptr[j + 1] = colptr[j] + len(r)
+    A = Csc.from_arrays(n, colptr, np.concatenate(ri), np.concatenate(vv), dtype)
+    return A, V
 
 
 def synth(blocks, seed, dtype, pivot=None):
@@ -98,39 +169,100 @@ def synth(blocks, seed, dtype, pivot=None):
             P[np.ix_(half, np.arange(f, l))] = True
             ragged_u(b, par)
         ragged_u(b, root)
-    npt = DTYPES[dtype]
-    V = rng.uniform(-1.0, 1.0, (n, n))
-    if dtype == SLU_Z:
-        V = V + 1j * rng.uniform(-1.0, 1.0, (n, n))
-    V = np.where(P, V, 0).astype(npt)
-    np.fill_diagonal(V, 0)
-    a = np.abs(V).astype(np.float64)
-    d = 1.05 * np.maximum(a.sum(axis=1), a.sum(axis=0)) + 1.0
-    if dtype == SLU_Z:
-        d = d * np.exp(2j * np.pi * rng.random(n))
-    else:
-        d = d * rng.choice([-1.0, 1.0], n)
-    V[np.arange(n), np.arange(n)] = d.astype(npt)
-    if pivot is not None:
-        pv = [pivot] if np.isscalar(pivot[0]) else list(pivot)
-        for col, val in pv:
-            V[col, :col] = 0      # stays in the pattern P: explicit stored zeros
-            V[col, col] = val
-    colptr = np.zeros(n + 1, dtype=np.int64)
-    ri, vv = [], []
-    for j in range(n):
-        r = np.nonzero(P[:, j])[0]
-        ri.append(r)
-        vv.append(V[r, j])
-        colptr[j + 1] = colptr[j] + len(r)
-    A = Csc.from_arrays(n, colptr, np.concatenate(ri), np.concatenate(vv), dtype)
-    return A, V
+    return _valued(P, rng, dtype, pivot)
 
 
-def symbolic(A):
+def sym_widths(spec):
+    """The prescribed partition of a synth_sym family: the arms' widths in
+    order, then the root."""
+    arms = [a["widths"] if isinstance(a, dict) else a for a in spec["arms"]]
+    return [w for a in arms for w in a] + [spec["root"]]
+
+
+def synth_sym(spec, seed, dtype, pivot=None):
+    """Returns (Csc, dense matrix) of a structurally symmetric, nested matrix
+    whose chains the engine's amalgamation merges (csrc/amalg.h; synth()'s
+    ragged U never does: U(s,:) lacks columns that L(:,s) has as rows).
+
+    spec: {"arms": [...], "root": width, the defaults "drop" (2), "keep"
+    (None), "ufirst" ("ragged"), and "maxsup", the symbolic stage's widest
+    supernode for this family (synth.case; 512 if absent)}; an arm is a list of widths, or a dict with
+    "widths" and its own drop / keep / ufirst.  Every arm is a chain of blocks
+    whose last block hangs on the root.  The rows of L(:,b) below the
+    diagonal block:
+
+      last block of an arm   a random 2/3 of the root's columns;
+      other blocks           cols(b+1) without ``drop`` random columns (at
+                             least one stays; with drop = 0 the symbolic stage
+                             makes b and b+1 one supernode unless the
+                             family's maxsup cuts them apart), plus the next block's row set --
+                             with ``keep``, only that many of it (negative:
+                             all but that many), which leaves explicit zeros
+                             in the coarse storage and keeps a width-1 block
+                             apart from a width-1 parent (drop = 0 there).
+
+    U(b,:) has exactly these columns, one entry of A in each: at a random row
+    of b ("ragged"), at b's first row ("top"), or at the given offsets from
+    b's first row (an array, cycled over the columns in ascending order; the
+    arm's first block only, the others "top").  Elimination of block b - 1
+    fills the columns it shares with b from b's first row that b - 1 holds,
+    so prescribed first rows are exact in an arm's first block.
+    The first column of the next block (of the root) is always among the
+    rows: every block then hangs on its parent's first column in the
+    elimination tree, whose postorder is the order written, so perm_c is the
+    identity and the partition comes out as requested (with a later first row
+    the symbolic stage's postorder moves the arm).  Values, pivot: as synth()."""
+    rng = np.random.default_rng(seed)
+    arms = [dict(a) if isinstance(a, dict) else {"widths": a} for a in spec["arms"]]
+    widths = sym_widths(spec)
+    xs = np.concatenate([[0], np.cumsum(widths)]).astype(np.int64)
+    n = int(xs[-1])
+    root = len(widths) - 1
+    P = np.zeros((n, n), dtype=bool)
+    P[xs[root]:, xs[root]:] = True
+    rr = np.arange(xs[root], xs[root + 1])
+    b0 = 0
+    for arm in arms:
+        nb = len(arm["widths"])
+        drop, keep, ufirst = (arm.get(k, spec.get(k, d)) for k, d in
+                              (("drop", 2), ("keep", None), ("ufirst", "ragged")))
+        below = None
+        for b in range(b0 + nb - 1, b0 - 1, -1):       # from the arm's last block up
+            f, l = int(xs[b]), int(xs[b + 1])
+            if below is None:
+                rows = np.sort(np.concatenate([rr[:1], rng.choice(rr[1:], size=max(1, (2 * len(rr)) // 3) - 1,
+                                                                     replace=False)]))
+            else:
+                nxt = np.arange(xs[b + 1], xs[b + 2])
+                d = min(drop, len(nxt) - 1)              # (at least one row of the parent stays)
+                assert d or keep is not None or "maxsup" in spec, \
+                    "drop = 0 without keep or a maxsup: the symbolic stage merges b and b + 1"
+                if d:
+                    nxt = np.sort(np.concatenate([nxt[:1], rng.choice(nxt[1:], size=len(nxt) - d - 1,
+                                                                      replace=False)]))
+                if keep is not None:
+                    k = keep if keep >= 0 else len(below) + keep
+                    below = np.sort(rng.choice(below, size=max(1, min(k, len(below))), replace=False))
+                rows = np.concatenate([nxt, below])
+            P[f:l, f:l] = True
+            P[np.ix_(rows, np.arange(f, l))] = True
+            if isinstance(ufirst, str):
+                assert ufirst in ("ragged", "top")
+                off = rng.integers(0, l - f, len(rows)) if ufirst == "ragged" else np.zeros(len(rows), int)
+            else:
+                off = np.resize(np.asarray(ufirst, dtype=int), len(rows)) if b == b0 else np.zeros(len(rows), int)
+                assert ((0 <= off) & (off < l - f)).all()
+            P[f + off, rows] = True
+            below = rows
+        b0 += nb
+    return _valued(P, rng, dtype, pivot)
+
+
+def symbolic(A, maxsup=MAXSUP):
     """The reference symbolic stage on the natural order; the front-end's own
-    partitions these matrices differently."""
-    return Symbolic(A, np.arange(A.n, dtype=np.int64), relax=1, maxsup=MAXSUP, reference=True)
+    partitions these matrices differently.  maxsup: the widest supernode (a
+    family of SYM_FAMILIES may set its own)."""
+    return Symbolic(A, np.arange(A.n, dtype=np.int64), relax=1, maxsup=maxsup, reference=True)
 
 
 def dense_lu_ref(V, thresh=None):
@@ -235,6 +367,31 @@ def lu_to_dense(lu, n):
     return M
 
 
+def levels(lu):
+    """Level of every supernode of a 1x1 LUstruct as the plan counts them
+    (csrc/engine.hip: a supernode comes one level after the last one that
+    updates it, i.e. that has it among its L block rows or U block columns)."""
+    xs = lu.xsup
+    lev = np.zeros(lu.nsupers, dtype=np.int64)
+    for k in range(lu.nsupers):
+        tg = set()
+        idx = lu.Lidx[lu.Loff[k]:]
+        p = 2
+        for _ in range(idx[0]):
+            tg.add(int(idx[p]))
+            p += 2 + idx[p + 1]
+        if lu.Uoff[k] >= 0:
+            idx = lu.Uidx[lu.Uoff[k]:]
+            p = 3
+            for _ in range(idx[0]):
+                jb = int(idx[p])
+                tg.add(jb)
+                p += 2 + xs[jb + 1] - xs[jb]
+        for t in tg - {k}:
+            lev[t] = max(lev[t], lev[k] + 1)
+    return lev
+
+
 def u_first_rows(lu):
     """(block, first row of the segment - first row of the block) of every
     nonempty U segment."""
@@ -277,6 +434,9 @@ def lu_errors(M, R, upto=None):
 @functools.lru_cache(maxsize=None)
 def case(family, dtype, pivot=None, seed=7):
     """(A, S, dense V, anorm) of a family; cached, treat as read-only."""
+    if family in SYM_FAMILIES:
+        A, V = synth_sym(SYM_FAMILIES[family], seed, dtype, pivot)
+        return A, symbolic(A, SYM_FAMILIES[family].get("maxsup", MAXSUP)), V, cases.anorm(A)
     A, V = synth(FAMILIES[family], seed, dtype, pivot)
     return A, symbolic(A), V, cases.anorm(A)
 

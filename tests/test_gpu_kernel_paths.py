@@ -6,8 +6,10 @@ Every case is one factorization of n <= 800 on one process: info and the tiny
 count exact, L and U within test_oracle.TOL of dense_lu_ref (error = max|mine -
 ref| / max|ref|, L and U separately), and where info == 0 also within TOL of
 the oracle.  The width sweeps run with SLU_AMALG=0 so that the plan factors the
-prescribed partition; each family runs once more with the default
-amalgamation, parity only.
+prescribed partition; some run once more in the default environment, where
+nothing of them merges and the plain plan runs again (test_default_amalgamation),
+and two mergeable families of synth_sym run through the amalgamated plan
+(test_merging_amalgamation).
 
 Which case asserts which counter non-zero:
 
@@ -58,10 +60,11 @@ def oracle_dense(family, dtype, pivot, replace_tiny):
     return synth.lu_to_dense(ref, A.n), o
 
 
-def run(family, dtype, pivot=None, replace_tiny=False):
+def run(family, dtype, pivot=None, replace_tiny=False, stats=None):
     """One factorization checked against the long-double LU and the oracle;
     returns (info, tiny, path counts).  Pivot cases compare what
-    synth.final_upto calls well defined; info is pinned by the callers."""
+    synth.final_upto calls well defined; info is pinned by the callers.
+    stats: a dict that receives the plan's stats."""
     A, S, V, an = synth.case(family, dtype, pivot)
     gpu = S.distribute()
     p = Plan(gpu, replace_tiny=replace_tiny)
@@ -69,6 +72,8 @@ def run(family, dtype, pivot=None, replace_tiny=False):
     info, tiny = p.factor(synth.norm_for(an, replace_tiny))
     p.download()
     pc = p.path_counts()
+    if stats is not None:
+        stats.update(p.stats())
     R, rinfo, rtiny = synth.reference(family, dtype, pivot, replace_tiny)
     upto = synth.final_upto(pivot, replace_tiny)
     M = synth.lu_to_dense(gpu, A.n)
@@ -197,8 +202,30 @@ def test_complex(family, monkeypatch):
 @pytest.mark.parametrize("family,dtype", [(f, d) for f in ("narrow_star", "edge_chain", "wide_chain",
                                                           "mixed_star") for d in (0, 1)] +
                          [("narrow_star", 2), ("edge_chain", 2)])
-def test_default_amalgamation(family, dtype):
-    run(family, dtype)
+def test_default_amalgamation(family, dtype, monkeypatch):
+    """The default environment on structures that do not merge: synth()'s
+    ragged U rows fail the symmetry test of the amalgamation
+    (tests/test_synth.py::test_ragged_families_do_not_merge), AmalgPlan::make
+    finds no chain and the plain plan runs the prescribed partition."""
+    monkeypatch.delenv("SLU_AMALG", raising=False)
+    monkeypatch.delenv("SLU_AMALG_ZERO", raising=False)
+    st = {}
+    run(family, dtype, stats=st)
+    assert st["amalg_groups"] == 0 and st["nsupers"] == st["nsupers_in"] == len(synth.FAMILIES[family])
+
+
+@pytest.mark.parametrize("family,dtype", [(f, d) for f in ("amalg_mixed", "amalg_uchunk") for d in (0, 1, 2)])
+def test_merging_amalgamation(family, dtype, monkeypatch):
+    """The default environment on structures that merge (synth_sym): the
+    amalgamated plan factors the coarse partition, the factors come back in
+    the caller's layout (tests/test_gpu_amalg_shapes.py has the relayout's
+    own tests)."""
+    monkeypatch.delenv("SLU_AMALG", raising=False)
+    monkeypatch.delenv("SLU_AMALG_ZERO", raising=False)
+    st = {}
+    run(family, dtype, stats=st)
+    assert st["amalg_groups"] > 0 and st["nsupers"] < st["nsupers_in"]
+    assert st["nsupers_in"] == len(synth.sym_widths(synth.SYM_FAMILIES[family]))
 
 
 # ------------------------------------------------------------------ pivots
