@@ -312,6 +312,28 @@ int slu_plan_rcond_info(const slu_plan *p, int *sweeps, double *ms);
 int slu_plan_solve_block(slu_plan *p, void *b, int64_t ldb, int nrhs, int on_device);
 /* passes over the factors, kernel launches and device ms of the last call */
 int slu_plan_solve_block_info(const slu_plan *p, int *passes, int64_t *launches, double *ms);
+/* DiagInv for the block sweeps (the reference's options->DiagInv): on != 0 makes
+ * solve_block, refine_block and refine_block_d2 apply inverted diagonal blocks
+ * by GEMM (csrc/solve_block_inv.h); the inverses are (re)computed at the first
+ * block sweep after the device factors change.  on == 0 frees them.  1x1 plans
+ * only: 2D and 3D plans refuse the call.  Allowed before the plan holds
+ * factors (nothing runs on the device then).  The transposed block calls
+ * (slu_plan_solve_block_t / slu_plan_refine_block_t with trans != SLU_NOTRANS)
+ * keep substituting with the mode on, and slu_plan_solve, slu_plan_refine,
+ * slu_plan_rcond and the grid solve never look at it.  The inversion's device
+ * time is reported here alone, not in t_solve_ms / t_refine_ms. */
+int slu_plan_set_diag_inv(slu_plan *p, int on);
+/* mode, whether the inverses match the current factors, bytes held, how often
+ * they were computed over the plan's life, device ms of the last computation */
+int slu_plan_diag_inv_info(const slu_plan *p, int *on, int *valid, int64_t *bytes,
+                           int *computes, double *ms);
+/* supernode k of the swept partition: first column, width, and (out != NULL)
+ * its packed inverse, column-major with leading dimension ldo >= w: L_kk^-1
+ * strictly below the diagonal (unit diagonal implied), U_kk^-1 on and above
+ * it.  out is a host array of the plan's element type; asking for it needs
+ * the mode on and factors on the device, and computes the inverses first if
+ * they are not valid. */
+int slu_plan_diag_inv_block(slu_plan *p, int k, int *fst, int *w, void *out, int64_t ldo);
 /* Block iterative refinement (1x1 plans; 2D and 3D plans refused): the loop
  * of slu_plan_refine (refine_block) / slu_plan_refine_d2 (refine_block_d2)
  * on a pass of SVB_NR columns at once (32, 16 in complex;

@@ -50,6 +50,7 @@
 #include "solve.h"
 #include "solve_block.h"
 #include "solve_block_t.h"
+#include "solve_block_inv.h"
 #include "refine_d2.h"
 #include "refine_block.h"
 #include "hostio.h"
@@ -330,6 +331,11 @@ struct PlanBase {
     int svb_passes = 0;
     int64_t svb_launches = 0;
     double svb_ms = 0;
+    // DiagInv for the block sweep (1x1 plans; solve_block_inv.h): the mode,
+    // its state, and supernode k's first column, width and inverse block
+    virtual void set_diag_inv(int on) = 0;
+    virtual void diag_inv_info(int *on, int *valid, int64_t *bytes, int *computes, double *ms) = 0;
+    virtual void diag_inv_block(int k, int *fst, int *w, void *out, int64_t ldo) = 0;
     virtual void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) = 0;
     virtual void fill_a(const void *a, int on_device) = 0;
     virtual void refine(const void *b, void *x, int64_t ld, int nrhs, double *berr, int *steps) = 0;
@@ -2849,6 +2855,7 @@ struct Plan : PlanBase {
     // d_acur64 / a_fact64 / snap_acur64: the same for the fp64 values an
     // fp32 plan got through fill_a_d2 (then d_acur is null: no fp32 A exists).
     int vstate = 0;
+    bool dinv_valid = false; // DiagInv's inverses are those of the factors: cleared wherever vstate is assigned
     const T *a_fact = nullptr, *snap_acur = nullptr;
     const double *d_acur64 = nullptr, *a_fact64 = nullptr, *snap_acur64 = nullptr;
     int snap_state = 0;
@@ -2898,6 +2905,7 @@ struct Plan : PlanBase {
         stats.t_upload_wait_ms = ms_since(t0);
         stats.t_upload_ms = up_ms;
         vstate = 1;
+        dinv_valid = false;
         d_acur = nullptr;
         d_acur64 = nullptr;
         host_current = true;
@@ -3066,6 +3074,7 @@ struct Plan : PlanBase {
     void restore() override {
         SLU_REQUIRE(d_L0.p && d_U0.p, "restore without snapshot");
         vstate = snap_state;
+        dinv_valid = false;
         d_acur = snap_acur;
         d_acur64 = snap_acur64;
         host_current = false;
@@ -3080,6 +3089,7 @@ struct Plan : PlanBase {
         upload();
         sync();
         vstate = 2;
+        dinv_valid = false;
         a_fact = nullptr; // adopted factors: of no A this plan knows
         a_fact64 = nullptr;
     }
@@ -3466,6 +3476,7 @@ struct Plan : PlanBase {
                     vstate == 2 ? "already factored; upload / restore / fill_a first"
                                 : "upload or fill_a first");
         vstate = 2;
+        dinv_valid = false;
         a_fact = d_acur;
         a_fact64 = d_acur64;
         // thresh = smach_dist("Epsilon") * anorm (SRC/pdgstrf.c:412-413); in
@@ -3570,6 +3581,9 @@ struct Plan : PlanBase {
     bool sv_ready = false;
     vector<int> sv_d_off, sv_l_off, sv_u_off; // per level: diag items, L chunks, U chunks
     DevBuf<SvDiag> d_sv_diag, d_sv_lvl;       // per supernode / in level order
+    DevBuf<i64> d_sv_ioff;                    // beside d_sv_lvl: offset of each item's block of DiagInv's inverses
+    vector<i64> sv_ioff;                      // the same per supernode (-1: not this rank's), and their total
+    i64 sv_inv_total = 0;
     DevBuf<SvDiag> d_sv_pan;                  // per supernode: this rank's L rows below the diagonal block
     DevBuf<SvChunk> d_sv_lch, d_sv_uch;
     DevBuf<i64> d_sv_roff, d_sv_coff;
@@ -3649,11 +3663,15 @@ struct Plan : PlanBase {
                     "rows and columns; 1x1 plans only)", what, Pr, Pc);
         SLU_REQUIRE(vstate == 2, "%s: the device storage holds no factors (factor first)", what);
     }
-    // the same rules in the words of the block sweep's callers
-    void require_1x1_factors_block(const char *what = "solve_block") {
+    // the same rules in the words of the block sweep's callers; the grid
+    // part alone is what set_diag_inv refuses (it needs no factors)
+    void require_1x1_block(const char *what) {
         SLU_REQUIRE(!zmode, "%s: not on 3D plans (the block sweep runs on 1x1 plans only)", what);
         SLU_REQUIRE(!xmode, "%s: not on a %dx%d grid (the block sweep has no exchanges; "
                     "1x1 plans only)", what, Pr, Pc);
+    }
+    void require_1x1_factors_block(const char *what = "solve_block") {
+        require_1x1_block(what);
         SLU_REQUIRE(vstate == 2, "%s: the device storage holds no factors (factor first)", what);
     }
 
@@ -3738,6 +3756,9 @@ struct Plan : PlanBase {
             for (int c = 0; c < W(ublk_jb[b]); ++c) gc[ublk[b].coloff + c] = ublk[b].fcol + c;
         vector<SvChunk> lch, uch;
         vector<SvAdd> adds;
+        vector<i64> ioff;
+        sv_ioff.assign(nsupers, -1);
+        sv_inv_total = 0;
         sv_d_off.assign(nl + 1, 0);
         sv_l_off.assign(nl + 1, 0);
         sv_u_off.assign(nl + 1, 0);
@@ -3751,7 +3772,12 @@ struct Plan : PlanBase {
             sv_add_off[L] = (int)adds.size();
             i64 slot = 0;
             for (int k : bylev[L]) {
-                if (sv_own[k]) lvl.push_back(dg[k]);
+                if (sv_own[k]) {
+                    lvl.push_back(dg[k]);
+                    sv_ioff[k] = sv_inv_total;
+                    ioff.push_back(sv_inv_total);
+                    sv_inv_total += (i64)W(k) * W(k);
+                }
                 for (int r0 = 0; r0 < pan[k].pad; r0 += SV_THREADS) lch.push_back({k, r0});
                 for (int c0 = 0; c0 < ncol[k]; c0 += SVU_COLS) uch.push_back({k, c0});
                 if (k % Pr != myrow) continue;
@@ -3775,6 +3801,7 @@ struct Plan : PlanBase {
         d_sv_diag.upload(dg);
         d_sv_pan.upload(pan);
         d_sv_lvl.upload(lvl.empty() ? vector<SvDiag>(1) : lvl);
+        d_sv_ioff.upload(ioff.empty() ? vector<i64>(1, 0) : ioff);
         d_sv_lch.upload(lch.empty() ? vector<SvChunk>(1) : lch);
         d_sv_uch.upload(uch.empty() ? vector<SvChunk>(1) : uch);
         d_sv_roff.upload(roff);
@@ -3895,17 +3922,82 @@ struct Plan : PlanBase {
     // ---- block solve (solve_block.h): SvbNr right-hand sides per pass over
     // the factors, in a row-major working buffer allocated on first use
     DevBuf<T> d_svb_x, d_svb_stage;
+
+    // ---- DiagInv (solve_block_inv.h): with the mode on, sweep_block applies
+    // inverted diagonal blocks by MFMA products.  The inverses are those of
+    // the device factors while dinv_valid holds; a block sweep's caller
+    // recomputes them first when it does not (diag_inv_ensure), outside the
+    // sweep's own timers.  The transposed block sweep keeps substituting.
+    bool dinv_on = false;
+    DevBuf<T> d_svb_inv; // sv_inv_total elements at d_sv_ioff's offsets, allocated at the first computation
+    int dinv_computes = 0;
+    double dinv_ms = 0;
+    void set_diag_inv(int on) override {
+        require_1x1_block("set_diag_inv");
+        dinv_on = on != 0;
+        if (!dinv_on) {
+            d_svb_inv.release();
+            dinv_valid = false;
+        }
+    }
+    void diag_inv_info(int *on, int *valid, int64_t *bytes, int *computes, double *ms) override {
+        if (on) *on = dinv_on;
+        if (valid) *valid = dinv_on && dinv_valid;
+        if (bytes) *bytes = (int64_t)d_svb_inv.bytes();
+        if (computes) *computes = dinv_computes;
+        if (ms) *ms = dinv_ms;
+    }
+    // every diagonal block of the device factors inverted into d_svb_inv: one
+    // launch, timed on its own
+    void diag_inv_compute() {
+        if (!sv_ready) build_solve();
+        if (d_svb_inv.n != (size_t)sv_inv_total) d_svb_inv.alloc((size_t)sv_inv_total);
+        const int nd = sv_d_off[bylev.size()];
+        EventTimer tm;
+        HIPCHK(hipStreamSynchronize(pstream));
+        tm.start(stream);
+        if (nd)
+            hipLaunchKernelGGL(k_svb_inv<T>, dim3(nd), dim3(SVB_ITHREADS), 0, stream, (const SvDiag *)d_sv_lvl.p,
+                               (const T *)d_L.p, (const i64 *)d_sv_ioff.p, d_svb_inv.p);
+        HIPCHK(hipGetLastError());
+        tm.stop(stream);
+        dinv_ms = tm.ms();
+        ++dinv_computes;
+        dinv_valid = true;
+    }
+    void diag_inv_ensure() {
+        if (dinv_on && !dinv_valid) diag_inv_compute();
+    }
+    void diag_inv_block(int k, int *fst, int *w, void *out, int64_t ldo) override {
+        require_1x1_block("diag_inv_block");
+        SLU_REQUIRE(k >= 0 && k < nsupers, "diag_inv_block: supernode %d is none of the plan's %d", k, nsupers);
+        const int wk = W(k);
+        if (fst) *fst = (int)xsup[k];
+        if (w) *w = wk;
+        if (!out) return;
+        SLU_REQUIRE(ldo >= wk, "diag_inv_block: ldo %lld < the supernode's width %d", (long long)ldo, wk);
+        SLU_REQUIRE(dinv_on, "diag_inv_block: the mode is off (slu_plan_set_diag_inv first)");
+        SLU_REQUIRE(vstate == 2, "diag_inv_block: the device storage holds no factors (factor first)");
+        diag_inv_ensure();
+        HIPCHK(hipStreamSynchronize(stream));
+        HIPCHK(hipMemcpy2D(out, (size_t)ldo * sizeof(T), d_svb_inv.p + sv_ioff[k], (size_t)wk * sizeof(T),
+                           (size_t)wk * sizeof(T), (size_t)wk, hipMemcpyDeviceToHost));
+    }
     // the level order of sweep_nr on the row-major X; returns the launches
     i64 sweep_block(T *xb) {
         const int nl = (int)bylev.size();
         i64 nk = 0;
+        const bool inv = dinv_on; // the callers have made the inverses valid (diag_inv_ensure)
+        const T *mi = d_svb_inv.p;
         for (int L = 0; L < nl; ++L) { // L Y = B
-            nk += sv_diag(L, k_svb_ldiag<T>, SVB_DTHREADS, xb);
+            nk += inv ? sv_diag(L, k_svb_minv<T, false>, SVB_ITHREADS, d_sv_ioff.p + sv_d_off[L], mi, xb)
+                      : sv_diag(L, k_svb_ldiag<T>, SVB_DTHREADS, xb);
             nk += sv_lpan(L, k_svb_lpanel<T>, SVB_LTHREADS, xb);
         }
         for (int L = nl - 1; L >= 0; --L) { // U X = Y
             nk += sv_upan(L, k_svb_upanel<T>, SV_THREADS, xb);
-            nk += sv_diag(L, k_svb_udiag<T>, SVB_DTHREADS, xb);
+            nk += inv ? sv_diag(L, k_svb_minv<T, true>, SVB_ITHREADS, d_sv_ioff.p + sv_d_off[L], mi, xb)
+                      : sv_diag(L, k_svb_udiag<T>, SVB_DTHREADS, xb);
         }
         HIPCHK(hipGetLastError());
         return nk;
@@ -3947,6 +4039,7 @@ struct Plan : PlanBase {
         stats.t_solve_ms = 0;
         if (nrhs == 0 || n == 0) return;
         if (!sv_ready) build_solve();
+        if (!trans) diag_inv_ensure();
         constexpr int NRB = SvbNr<T>::v;
         const size_t nn = (size_t)n;
         if (d_svb_x.n < nn * NRB) d_svb_x.alloc(nn * NRB);
@@ -4389,6 +4482,7 @@ struct Plan : PlanBase {
             hipLaunchKernelGGL(k_rfb_axpy<T>, dim3(eb), dim3(RFB_THREADS), 0, stream, xb, (const T *)rb, total, act);
         };
         if (!trans) {
+            if (ld >= n && nrhs > 0 && n > 0) diag_inv_ensure();
             refine_block_loop<T, false>(what, eps, b, x, ld, nrhs, on_device, berr, steps,
                                         rfb_resid_rows<T, false>(a_fact, safe1, safe2), step);
             return;
@@ -4418,6 +4512,7 @@ struct Plan : PlanBase {
             const i64 total = (i64)n * NRB;
             const unsigned eb = (unsigned)((total + RFB_THREADS - 1) / RFB_THREADS);
             if (ld >= n && nrhs > 0 && d_svb_x.n < (size_t)total) d_svb_x.alloc((size_t)total);
+            if (ld >= n && nrhs > 0 && n > 0) diag_inv_ensure();
             refine_block_loop<double, true>(
                 "refine_block_d2", eps, b, x, ld, nrhs, on_device, berr, steps,
                 rfb_resid_rows<double, true>(a_fact64, safe1, safe2),
@@ -4696,6 +4791,7 @@ struct Plan : PlanBase {
     // zero this rank's L and U, scatter A's values with `launch`; t_fill_ms
     template <typename F> void fill_storage(F &&launch) {
         vstate = 1;
+        dinv_valid = false;
         host_current = false;
         EventTimer tm;
         HIPCHK(hipStreamSynchronize(pstream));
@@ -5002,6 +5098,24 @@ int slu_plan_solve_block_info(const slu_plan *p, int *passes, int64_t *launches,
     if (launches) *launches = p->impl->svb_launches;
     if (ms) *ms = p->impl->svb_ms;
     return 0;
+}
+
+int slu_plan_set_diag_inv(slu_plan *p, int on) {
+    return guarded([&] {
+        p->impl->set_diag_inv(on);
+    });
+}
+
+int slu_plan_diag_inv_info(const slu_plan *p, int *on, int *valid, int64_t *bytes, int *computes, double *ms) {
+    return guarded([&] {
+        p->impl->diag_inv_info(on, valid, bytes, computes, ms);
+    });
+}
+
+int slu_plan_diag_inv_block(slu_plan *p, int k, int *fst, int *w, void *out, int64_t ldo) {
+    return guarded([&] {
+        p->impl->diag_inv_block(k, fst, w, out, ldo);
+    });
 }
 
 int slu_plan_set_a_pattern(slu_plan *p, int64_t ncol, const int64_t *xa, const int64_t *asub) {

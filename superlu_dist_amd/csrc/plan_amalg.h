@@ -99,6 +99,13 @@ struct CoarsePlan : PlanBase {
         in->solve_block_t(trans, b, ldb, nrhs, on_device);
         sync_svb();
     }
+    void set_diag_inv(int on) override { in->set_diag_inv(on); }
+    void diag_inv_info(int *on, int *valid, int64_t *bytes, int *computes, double *ms) override {
+        in->diag_inv_info(on, valid, bytes, computes, ms);
+    }
+    void diag_inv_block(int k, int *fst, int *w, void *out, int64_t ldo) override {
+        in->diag_inv_block(k, fst, w, out, ldo);
+    }
     void set_a_pattern(int64_t ncol, const int64_t *xa, const int64_t *asub) override {
         in->set_a_pattern(ncol, xa, asub);
         sync_stats();
@@ -584,6 +591,7 @@ struct AmalgPlan : CoarsePlan<T, HT, LocalLU, LUS> {
         relayout(0);
         t_expand = ms_since(t1);
         in->vstate = 1;
+        in->dinv_valid = false;
         in->d_acur = nullptr;
         in->d_acur64 = nullptr;
         in->host_current = false;
@@ -596,6 +604,7 @@ struct AmalgPlan : CoarsePlan<T, HT, LocalLU, LUS> {
         upload();
         in->sync();
         in->vstate = 2;
+        in->dinv_valid = false;
         in->a_fact = nullptr; // adopted factors: of no A this plan knows
         in->a_fact64 = nullptr;
         coarse_current = true;
@@ -872,6 +881,7 @@ struct GridAmalgPlan : CoarsePlan<T, HT, LocalLU, LUS> {
         t_h2d = ms_since(t0);
         expand();
         in->vstate = 1;
+        in->dinv_valid = false;
         in->d_acur = nullptr;
         in->d_acur64 = nullptr;
         in->host_current = false;
@@ -882,6 +892,7 @@ struct GridAmalgPlan : CoarsePlan<T, HT, LocalLU, LUS> {
         upload();
         in->sync();
         in->vstate = 2;
+        in->dinv_valid = false;
         in->a_fact = nullptr; // adopted factors: of no A this plan knows
         in->a_fact64 = nullptr;
     }

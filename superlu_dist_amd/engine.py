@@ -246,6 +246,34 @@ class Plan:
         lib().slu_plan_solve_block_info(self.ptr, C.byref(k), C.byref(nl), C.byref(ms))
         return k.value, nl.value, ms.value
 
+    def set_diag_inv(self, on=True):
+        """DiagInv for the block sweeps (the reference's options->DiagInv):
+        solve_block, refine_block and refine_block_d2 apply inverted diagonal
+        blocks by MFMA products instead of substituting.  The inverses are
+        (re)computed at the first block sweep after the device factors change;
+        on=False frees them.  1x1 plans; trans="T" / "C" keep substituting."""
+        self._chk(lib().slu_plan_set_diag_inv(self.ptr, int(bool(on))))
+
+    def diag_inv_info(self):
+        """(on, valid, bytes held, computations over the plan's life, device ms
+        of the last computation) of DiagInv."""
+        on, valid, nc, nb, ms = C.c_int(), C.c_int(), C.c_int(), C.c_int64(), C.c_double()
+        self._chk(lib().slu_plan_diag_inv_info(self.ptr, C.byref(on), C.byref(valid), C.byref(nb),
+                                               C.byref(nc), C.byref(ms)))
+        return bool(on.value), bool(valid.value), nb.value, nc.value, ms.value
+
+    def diag_inv_block(self, k):
+        """(first column, inverse) of supernode k of the swept partition: a
+        (w, w) array with L_kk^-1 strictly below the diagonal (its unit
+        diagonal implied) and U_kk^-1 on and above it.  Needs the mode on and
+        factors on the device; computes the inverses if they are not valid."""
+        fst, w = C.c_int(), C.c_int()
+        self._chk(lib().slu_plan_diag_inv_block(self.ptr, int(k), C.byref(fst), C.byref(w), None, 0))
+        out = np.zeros((w.value, w.value), dtype=self.lu.Lval.dtype, order="F")
+        self._chk(lib().slu_plan_diag_inv_block(self.ptr, int(k), None, None,
+                                                out.ctypes.data_as(C.c_void_p), max(w.value, 1)))
+        return fst.value, out
+
     def set_a_pattern(self, colptr, rowind):
         """Pattern of A in the LUstruct's permuted coordinates (CSC)."""
         self._xa = np.ascontiguousarray(colptr, dtype=np.int64)

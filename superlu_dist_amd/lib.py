@@ -179,6 +179,10 @@ def lib():
         "slu_plan_rcond_info": (C.c_int, [P, c_intp, C.POINTER(C.c_double)]),
         "slu_plan_solve_block": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_int]),
         "slu_plan_solve_block_info": (C.c_int, [P, c_intp, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+        "slu_plan_set_diag_inv": (C.c_int, [P, C.c_int]),
+        "slu_plan_diag_inv_info": (C.c_int, [P, c_intp, c_intp, C.POINTER(C.c_int64), c_intp,
+                                             C.POINTER(C.c_double)]),
+        "slu_plan_diag_inv_block": (C.c_int, [P, C.c_int, c_intp, c_intp, P, C.c_int64]),
         "slu_plan_fill_a_d2": (C.c_int, [P, P, C.c_int]),
         "slu_plan_refine_d2": (C.c_int, [P, P, P, C.c_int64, C.c_int, C.POINTER(C.c_double),
                                          c_intp]),
