@@ -1232,11 +1232,14 @@ constexpr int SB_BM = 128;
 constexpr size_t SB_UGUARD = 1024;
 // THREADS / WN: workgroup size and waves along N; MINW: waves per SIMD the
 // register budget must allow (workgroups per CU x waves per workgroup / 4).
+// FLAT: a fused tile runs both K segments through one stage loop.
 template <typename T> struct BigCfg {
     static constexpr int THREADS = 512, WN = 2, MINW = 4, BN = 128, BK = 16, FN = 4, PASSW = 64;
+    static constexpr bool FLAT = true;
 };
 template <> struct BigCfg<zc> {
     static constexpr int THREADS = 512, WN = 2, MINW = 4, BN = 64, BK = 8, FN = 2, PASSW = 16;
+    static constexpr bool FLAT = true;
 };
 // fp32: three workgroups per CU (6 waves per SIMD, <= 80 VGPRs; 42 KB LDS each)
 // (SLU_F32_BK / SLU_F32_MINW: A/B builds, tools/ab_build.sh)
@@ -1248,6 +1251,9 @@ template <> struct BigCfg<zc> {
 #endif
 template <> struct BigCfg<float> {
     static constexpr int THREADS = 512, WN = 2, MINW = SLU_F32_MINW, BN = 128, BK = SLU_F32_BK, FN = 4, PASSW = 64;
+    // at 80 VGPRs the flat loop's exact-pair kernel spills 9 VGPRs (4 with a
+    // loop per segment), two of them reloaded inside the epilogue's pass loop
+    static constexpr bool FLAT = false;
 };
 constexpr int SB_BN = BigCfg<double>::BN;
 constexpr int SB_THREADS = 512; // the 512-thread configurations (k_schur_big<float>, <zc>)
@@ -1257,7 +1263,8 @@ constexpr int SB_THREADS = 512; // the 512-thread configurations (k_schur_big<fl
 // phase timestamps of k_schur_big, read back by the engine after a factor()
 // (SLU_STAMP_OUT) and summarised by tools/stamp_analyze.py.  Four u64 per
 // tile: realtime start (40 b) + duration (24 b, 100 MHz) | prologue, K-loop
-// cycles | epilogue cycles, HW_ID | XCC_ID, tile shape, workgroup id.
+// cycles | epilogue cycles, HW_ID | XCC_ID, tile shape, workgroup id (bit 31:
+// fused tile, bit 63: of a mapped pair).
 constexpr unsigned SLU_STAMP_MAX = 1u << 21;
 __device__ uint64_t slu_stamp[SLU_STAMP_MAX * 4];
 __device__ unsigned slu_stamp_n;
@@ -1319,6 +1326,8 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
     SB_STAMP(c0_);
     const TileItem ti = tiles[blockIdx.x];
     const KInfo<T> ki = kinfo[ti.kslot];
+    // fused: the first segment's descriptor, fetched in the same scalar round
+    const KInfo<T> k1 = kinfo[FUSED ? ti.seg : ti.kslot];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid / WN, wc = wid % WN;
     const int row0 = ti.tm * SB_BM, col0 = ti.tn * SB_BN;
@@ -1357,12 +1366,20 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
     const bool avalid = ar < mrows;
     const int bc = tid / (SB_BK / BE), bk = (tid % (SB_BK / BE)) * BE;
     const bool bvalid = bc < ncols;
+    // FUSED == 2: the thread's A rows in the first segment (KInfo::mapped row
+    // map, -1 = absent), fetched in the same round as the tables above
+    constexpr bool FLAT = FUSED && BigCfg<T>::FLAT; // (else: one stage loop per segment)
+    int q0 = -1, q1 = -1;
+    if constexpr (FUSED == 2 && FLAT) {
+        if (ar < mrows) q0 = k1.rg[row0 + ar];
+        if (A16 && ar + 1 < mrows) q1 = k1.rg[row0 + ar + 1];
+    }
     // The K segment under way: the operands of one supernode's update.  A
     // fused tile (FUSED; ti.seg != ti.kslot) runs the far part of the pair's first
     // member, then the second member's own update, into the same
     // accumulators; both cover the tile's rows and columns from (row0, col0)
-    // of their KInfo.  The per-thread pointers are recomputed at the segment
-    // boundary rather than kept live (VGPR budget).
+    // of their KInfo.  The per-thread pointers are rewritten in place at the
+    // segment boundary rather than kept live for both (VGPR budget).
     const T *ap, *ub; // ub[t] valid for bt0 <= t < kmin + kw
     int bt0, kmin, kw, lda, tlast;
     // FUSED == 2: bit 0 (1): the thread's first (second, A16) row is present
@@ -1380,6 +1397,17 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
         if constexpr (APK_LDS) ((volatile int *)s_apk)[tid] = v;
         else apk = v;
     };
+    // The second segment's per-column tables wait in LDS from the prologue,
+    // so the switch inside the stage loop issues no global load.
+    __shared__ int s_nbt0[FLAT ? SB_BN : 1];
+    __shared__ int64_t s_ncv[FLAT ? SB_BN : 1];
+    if constexpr (FLAT)
+        if (tid >= SB_THREADS - SB_BN) {
+            const int c = tid - (SB_THREADS - SB_BN), cc = col0 + (c < ncols ? c : 0);
+            s_nbt0[c] = ki.ct0[cc];
+            s_ncv[c] = ki.cvoff[cc];
+        }
+    // `first`: the first segment of a fused tile (FUSED == 2: through its row map)
     auto segment = [&](const KInfo<T> &k, bool first) {
         kmin = k.kmin;
         kw = k.kw;
@@ -1390,22 +1418,27 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
         int t = tid;
         if constexpr (FUSED) asm volatile("" : "+v"(t));
         const int ar_ = A16 ? 2 * (t & 63) : t & (SB_BM - 1), bc_ = t / (SB_BK / BE);
-        const int bcc = col0 + (bc_ < ncols ? bc_ : 0);
-        if constexpr (FUSED == 2) {
-            if (first) { // through the row map
-                const int q0 = ar_ < mrows ? k.rg[row0 + ar_] : -1;
-                const int q1 = A16 && ar_ + 1 < mrows ? k.rg[row0 + ar_ + 1] : -1;
-                ap = k.a + max(q0, 0);
-                apk_set((max(q1, 0) - max(q0, 0)) * 4 + (q0 >= 0) + 2 * (q1 >= 0));
-            } else {
-                ap = k.a + row0 + (ar_ < mrows ? ar_ : 0);
-                apk_set((ar_ + 1 < mrows) * 6 + (ar_ < mrows));
+        if (FUSED == 2 && first) {
+            if constexpr (!FLAT) {
+                q0 = ar_ < mrows ? k.rg[row0 + ar_] : -1;
+                q1 = A16 && ar_ + 1 < mrows ? k.rg[row0 + ar_ + 1] : -1;
             }
+            ap = k.a + max(q0, 0);
+            apk_set((max(q1, 0) - max(q0, 0)) * 4 + (q0 >= 0) + 2 * (q1 >= 0));
+        } else if constexpr (FUSED == 2) {
+            ap = k.a + row0 + (ar_ < mrows ? ar_ : 0);
+            apk_set((ar_ + 1 < mrows) * 6 + (ar_ < mrows));
         } else {
             ap = k.a + row0 + (A16 || ar_ < mrows ? ar_ : 0);
         }
-        bt0 = k.ct0[bcc];
-        ub = k.ubase + k.cvoff[bcc] - bt0;
+        if (FLAT && !first) { // the tile's own columns: from the LDS tables
+            bt0 = s_nbt0[bc_];
+            ub = k.ubase + s_ncv[bc_] - bt0;
+        } else {
+            const int bcc = col0 + (bc_ < ncols ? bc_ : 0);
+            bt0 = k.ct0[bcc];
+            ub = k.ubase + k.cvoff[bcc] - bt0;
+        }
     };
     // The zeroing of out-of-range elements happens at the LDS store, after
     // the current stage's MFMAs, so the prefetch's latency is not waited on
@@ -1498,29 +1531,62 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
     };
     // The stage loop stays the only MFMA site besides the peeled last stage
     // (a copy of the stage body at the segment boundary made the compiler
-    // move the accumulators through scratch).  A segment that is not the
-    // last runs all its stages in the loop: its last stage prefetches itself
-    // once more (unused), then the next segment starts from a drained
-    // pipeline; each segment pads its own K to SB_BK.
+    // move the accumulators through scratch).  One loop runs the stages of
+    // both segments: the iteration that consumes the first segment's last
+    // stage switches the operands to the second and prefetches its first
+    // stage, so the pipeline never drains.  Each segment pads its own K to
+    // SB_BK, so every accumulator sees the MFMA sequence of two loops.
     int buf = 0; // the LDS buffer that holds the current stage
-    for (int left = FUSED ? 1 : 0;; --left) {
-        segment(kinfo[left ? ti.seg : ti.kslot], left != 0);
+    if constexpr (FUSED && !FLAT) {
+        // fp32 (BigCfg<float>::FLAT): one stage loop per segment.  The first
+        // segment's last stage prefetches itself once more (unused), then the
+        // second starts from a drained pipeline.
+        for (int left = 1;; --left) {
+            segment(kinfo[left ? ti.seg : ti.kslot], left != 0);
+            gload(0);
+            lstore(buf, 0);
+            __syncthreads();
+#ifdef SLU_SB_STAMP
+            if (left) SB_STAMP(c1_);
+#endif
+            const int nst = (kw + SB_BK - 1) / SB_BK, nloop = nst - (left == 0);
+            for (int st = 0; st < nloop; ++st) {
+                const int k0 = min(st + 1, nst - 1) * SB_BK;
+                gload(k0);
+                mfma_stage(buf);
+                lstore(buf ^ 1, k0);
+                __syncthreads();
+                buf ^= 1;
+            }
+            if (left == 0) break;
+        }
+    } else {
+        if constexpr (FUSED) segment(k1, true);
+        else segment(ki, false);
         gload(0);
         lstore(buf, 0);
         __syncthreads();
-#ifdef SLU_SB_STAMP
-        if (left == (FUSED ? 1 : 0)) SB_STAMP(c1_); // the prologue ends with the first segment's first stage
-#endif
-        const int nst = (kw + SB_BK - 1) / SB_BK, nloop = nst - (left == 0);
+        SB_STAMP(c1_); // the prologue ends with the first segment's first stage
+        // stages of the first segment of a fused tile (an empty one still has
+        // its zero stage).  The tile's own segment has ki.kw >= 1 (the plan
+        // makes tiles only for a panel with a nonempty U column), so the
+        // loop reaches the switching iteration.
+        const int nst0 = FUSED ? max((kw + SB_BK - 1) / SB_BK, 1) : 0;
+        const int nloop = nst0 + (ki.kw + SB_BK - 1) / SB_BK - 1;
+        int base = 0; // loop index of the current segment's first stage
         for (int st = 0; st < nloop; ++st) {
-            const int k0 = min(st + 1, nst - 1) * SB_BK;
+            if constexpr (FUSED)
+                if (st + 1 == nst0) { // wave-uniform: SGPRs and one LDS read
+                    segment(ki, false);
+                    base = nst0;
+                }
+            const int k0 = (st + 1 - base) * SB_BK;
             gload(k0);
             mfma_stage(buf);
             lstore(buf ^ 1, k0);
             __syncthreads();
             buf ^= 1;
         }
-        if (left == 0) break;
     }
     // last stage (peeled: no prefetch, so its registers carry the second
     // half of the destination tables instead): per (row block, column) the
@@ -1715,7 +1781,7 @@ k_schur_big(const TileItem *tiles, const KInfo<T> *kinfo, T *Lval, T *Uval,
             o[2] = (uint64_t)(t[c3_] - t[c2_]) | ((uint64_t)hw << 32);
             o[3] = (uint64_t)(xcc & 15) | ((uint64_t)kw << 4) | ((uint64_t)mrows << 14) |
                    ((uint64_t)ncols << 22) | ((uint64_t)ki.atomic << 30) | ((uint64_t)(FUSED != 0) << 31) |
-                   ((uint64_t)blockIdx.x << 32);
+                   ((uint64_t)blockIdx.x << 32) | ((uint64_t)(FUSED == 2) << 63);
         }
     }
 #endif

@@ -27,12 +27,13 @@ def load(fn):
     nc = ((m >> 22) & 255).astype(np.int64)
     at = ((m >> 30) & 1).astype(np.int64)
     fu = ((m >> 31) & 1).astype(np.int64)  # fused tile: kw is its second segment's
+    mp = (m >> 63).astype(np.int64)        # fused tile of a mapped pair
     cu = (hw >> 8) & 15
     sh = (hw >> 12) & 1
     se = (hw >> 13) & 7
     cuid = ((xcc * 8 + se) * 2 + sh) * 16 + cu
     return dict(rt0=rt0, dur=dur, pro=pro, kl=kl, epi=epi, xcc=xcc, kw=kw, mr=mr, nc=nc,
-                at=at, fu=fu, cuid=cuid)
+                at=at, fu=fu, mp=mp, cuid=cuid)
 
 
 def main():
@@ -42,11 +43,14 @@ def main():
     print(f"{n} tiles, {len(np.unique(d['cuid']))} distinct CUs")
     full = (d["mr"] == 128) & (d["nc"] == 128)
     one = d["fu"] == 0
-    # (fused tiles apart: their K loop holds two segments and the boundary's
-    # drained pipeline, so "per stage" is over the second segment's stages only)
+    # (fused tiles apart: their K loop holds two segments -- and, in fp32,
+    # which keeps a loop per segment, the boundary's drained pipeline -- so
+    # "per stage" is over the second segment's stages only)
     for name, sel in (("all", np.ones(n, bool)), ("full 128x128, kw>=192", full & one & (d["kw"] >= 192)),
                       ("full, kw 256", full & one & (d["kw"] == 256)), ("kw<64", one & (d["kw"] < 64)),
-                      ("fused, full, kw 256", full & ~one & (d["kw"] == 256))):
+                      ("fused, full, kw 256", full & ~one & (d["kw"] == 256)),
+                      ("  exact pairs", full & ~one & (d["mp"] == 0) & (d["kw"] == 256)),
+                      ("  mapped pairs", full & ~one & (d["mp"] == 1) & (d["kw"] == 256))):
         if not sel.any():
             continue
         p, k, e, t = (x[sel].sum() for x in (d["pro"], d["kl"], d["epi"], tot))
@@ -56,12 +60,15 @@ def main():
               f"K cycles per 16-deep stage {(d['kl'][sel] / ((d['kw'][sel] + 15) // 16)).mean():7.0f}")
     # fused against two separate passes (full tiles, both segments kw 256 in a
     # 256-wide chain): the boundary's cost = fused K loop - 2 x one-segment K loop
-    f256, o256 = full & ~one & (d["kw"] == 256), full & one & (d["kw"] == 256)
-    if f256.any() and o256.any():
-        kf, ko = d["kl"][f256].mean(), d["kl"][o256].mean()
-        tf, to = tot[f256].mean(), tot[o256].mean()
-        print(f"fused tile {tf:9.0f} cycles against 2 x {to:9.0f} = {2 * to:9.0f} ({tf / (2 * to) - 1:+.1%}); "
-              f"K loop {kf:9.0f} against 2 x {ko:9.0f}: boundary {kf - 2 * ko:8.0f} cycles")
+    o256 = full & one & (d["kw"] == 256)
+    for name, f256 in (("fused", full & ~one & (d["kw"] == 256)),
+                       ("exact", full & ~one & (d["mp"] == 0) & (d["kw"] == 256)),
+                       ("mapped", full & ~one & (d["mp"] == 1) & (d["kw"] == 256))):
+        if f256.any() and o256.any():
+            kf, ko = d["kl"][f256].mean(), d["kl"][o256].mean()
+            tf, to = tot[f256].mean(), tot[o256].mean()
+            print(f"{name} tile {tf:9.0f} cycles against 2 x {to:9.0f} = {2 * to:9.0f} ({tf / (2 * to) - 1:+.1%}); "
+                  f"K loop {kf:9.0f} against 2 x {ko:9.0f}: boundary {kf - 2 * ko:8.0f} cycles")
     # cycles per realtime tick (100 MHz) -> clock
     sel = d["dur"] > 100
     print(f"shader clock ~ {np.median(tot[sel] / d['dur'][sel]) * 100:.0f} MHz")
