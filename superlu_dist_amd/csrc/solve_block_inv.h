@@ -41,15 +41,14 @@ __device__ __forceinline__ void svb_tri_mul(const T *Mi, int w, int lo, int hi, 
     using Sx = S<T>;
     using M = Mma<T>;
     constexpr int NF = SvbNr<T>::v / 16, NW = SVB_ITHREADS / 64;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
+    const auto [t, lane, wv, lr, lk] = svb_lane();
     const int nfr = (hi - lo + 15) / 16;
     for (int g0 = 0; g0 < nfr; g0 += NW) { // uniform: every wave meets the round's barrier
         const int g = UP ? g0 + wv : nfr - 1 - g0 - wv;
         const bool live = g >= 0 && g < nfr;
         const int f0 = lo + g * 16, i = f0 + lr;
         typename M::acc_t acc[NF];
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) acc[nf] = M::zero();
+        svb_acc_zero<T>(acc);
         if (live) {
             const int kb = UP ? f0 : lo, ke = UP ? hi : min(hi, f0 + 16);
             for (int k1 = kb; k1 < ke; k1 += 16) { // 4 + 4 NF loads in flight per lane
@@ -106,13 +105,12 @@ __device__ __forceinline__ void svb_inv_column(const T *Lb, int64_t ld, T *Mo, i
     using Sx = S<T>;
     using M = Mma<T>;
     constexpr int SVP = SvPanel<T>::v, NF = SVP / 16, NW = SVB_ITHREADS / 64;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
+    const auto [t, lane, wv, lr, lk] = svb_lane();
     const int nfr = (hi - lo + 15) / 16;
     for (int g = wv; g < nfr; g += NW) {
         const int f0 = lo + g * 16, i = f0 + lr;
         typename M::acc_t acc[NF];
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) acc[nf] = M::zero();
+        svb_acc_zero<T>(acc);
 #pragma unroll
         for (int k0 = 0; k0 < SVP; k0 += 4) {
             const int k = k0 + lk;

@@ -3,51 +3,33 @@
 // factors, tables, levels and row-major X of solve_block.h.  The roles of L
 // and U swap as in solve.h's transposed sweeps: U's row segments are pushed
 // forward (k_svb_utpanel), L's panels are pulled backward (k_svb_ltpanel), and
-// both diagonal solves work on the transposed triangle.  Included by
+// both diagonal solves are svb_diag on the transposed triangle.  Included by
 // engine.hip.
 //
 // Fragments are Mma<T>'s 16x16x4 with N = right-hand sides.  In every product
 // here the MFMA K index runs along the contiguous stored dimension of the
-// factor.  With the plain lane map A(m = lane & 15, k = lane >> 4) a wave's
-// load would touch 16 columns x 32 bytes; the MFMA sum does not care in which
-// order K is visited as long as A and B agree, so a lane owns a run of
-// SvbRun consecutive K (32 bytes, two 16-byte loads; the four lanes of a
-// column cover 128 contiguous bytes) and reads B's LDS rows by the same
-// permutation: step j of a K block of 4 SvbRun multiplies A(m, kb + lk R + j)
-// with B(kb + lk R + j, n).  A factor element is conjugated as it is loaded
-// (sv_cj); X never is.  Dead columns of a partial pass are zeros throughout.
+// factor, a lane owning a run of SvbRun consecutive K (svb_krun and
+// svb_krun_step in solve_block.h).  A factor element is conjugated as it is
+// loaded; X never is.  Dead columns of a partial pass are zeros throughout.
 #pragma once
 #include "solve_block.h"
 
 namespace slu {
 
-// elements of a lane's K run: 32 bytes
-template <typename T> struct SvbRun { static constexpr int v = 32 / (int)sizeof(T); };
-
-// v[j] = op(p[j]) for the j in [lo, hi) and zero elsewhere, j < R; elements
-// outside [lo, hi) are not loaded.  A run that lies inside goes by 16-byte
-// loads (sv_run; p is element-aligned only), one that crosses an end element
-// by element.
-template <typename T, int R>
-__device__ __forceinline__ void svb_krun(const T *p, int lo, int hi, int conj, T (&v)[R]) {
-    if (lo <= 0 && hi >= R) {
-        sv_run<R>(p, v);
-    } else {
-#pragma unroll
-        for (int j = 0; j < R; ++j) v[j] = (j >= lo && j < hi) ? gld(p + j) : S<T>::zero();
-    }
-#pragma unroll
-    for (int j = 0; j < R; ++j) v[j] = sv_cj(v[j], conj);
-}
-
-// U_kk^T Z = C_k (lower, non-unit), k_svb_ldiag's structure on the transposed
-// triangle.  Row t of U_kk^T is column t of the block (contiguous, ld apart
-// across t), so the panel's triangle is read along the columns of the block,
-// element by element under the triangle's mask: nothing past row j0 + nj - 1
-// of a column is addressed, whatever nj.  Substitution in LDS by lane q of
-// the first wave, the diagonal divided as Sx::div does (no reciprocal).  The
-// rows below a panel exist only under full panels; their fragments subtract
-// U(panel, rows)^T Z_panel with K along the column of the block.
+// U_kk^T Z = C_k: the transposed upper triangle with its diagonal, forward.
+// This is svb_diag<T, false, true> written out: instantiated from the shared
+// body the fp64 kernel compiled to a different block layout of the
+// substitution loop and measured 8 % slower (216.8 against 200.8 ms over the
+// 1000 launches of ten sweeps at lap3d 100^3), with no source difference to
+// pin it on, so this one kernel keeps its own text.  The fragment helpers
+// alone (svb_lane, svb_acc_zero, svb_krun_step, svb_row_sub in this text)
+// change its fp64 code as well, 455 to 500 instructions, so it uses none of
+// them; its complex arithmetic is S<zc>::fms as the compiler contracts it here
+// (see svb_fms).  Row t of U_kk^T is
+// column t of the block: the panel's triangle is read along the columns of
+// the block under the triangle's mask, the rows below a panel exist only
+// under full panels, and their fragments subtract U(panel, rows)^T Z_panel
+// with K along the column of the block.
 template <typename T>
 __global__ void __launch_bounds__(SVB_DTHREADS)
 k_svb_utdiag(const SvDiag *items, const T *Lval, T *xb, int conj) {
@@ -129,86 +111,11 @@ k_svb_utdiag(const SvDiag *items, const T *Lval, T *xb, int conj) {
     }
 }
 
-// L_kk^T Y = Z (upper, unit) from the strict lower triangle, k_svb_udiag's
-// structure from the last panel up.  The first panel visited may be partial
-// and has rows above it: a lane's K run there is cut at the panel's last row
-// (rows j0 + nj and below of a column belong to the L panel or to the next
-// column).
+// L_kk^T Y = Z: the transposed unit lower triangle, backward
 template <typename T>
 __global__ void __launch_bounds__(SVB_DTHREADS)
 k_svb_ltdiag(const SvDiag *items, const T *Lval, T *xb, int conj) {
-    using Sx = S<T>;
-    using M = Mma<T>;
-    constexpr int SVP = SvPanel<T>::v, NRB = SvbNr<T>::v, NF = NRB / 16, NW = SVB_DTHREADS / 64;
-    constexpr int R = SvbRun<T>::v, KB = 4 * R;
-    static_assert(SVP % KB == 0, "a panel is whole K blocks");
-    const SvDiag it = items[blockIdx.x];
-    const T *L = Lval + it.voff;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, lr = lane & 15, lk = lane >> 4;
-    const int w = it.w;
-    const int64_t ld = it.ld;
-    T *X = xb + (int64_t)it.fst * NRB;
-    __shared__ T s_t[SVP][SVP + SVB_CH]; // s_t[j][i] = op(L(j0 + j, j0 + i)), i < j; padded as in k_svb_ldiag
-    __shared__ T s_p[SVP + SVB_CH][NRB];
-    for (int e = t; e < SVB_CH * NRB; e += SVB_DTHREADS) s_p[SVP + e / NRB][e % NRB] = Sx::zero();
-    for (int e = t; e < SVP * SVB_CH; e += SVB_DTHREADS) s_t[e / SVB_CH][SVP + e % SVB_CH] = Sx::zero();
-    for (int j0 = ((w - 1) / SVP) * SVP; j0 >= 0; j0 -= SVP) {
-        const int nj = min(SVP, w - j0);
-        for (int e = t; e < SVP * SVP; e += SVB_DTHREADS) {
-            const int j = e % SVP, i = e / SVP; // j runs down column j0 + i of the block
-            s_t[j][i] = (i < j && j < nj) ? sv_cj(gld(L + (j0 + j) + (j0 + i) * ld), conj) : Sx::zero();
-        }
-        for (int e = t; e < SVP * NRB; e += SVB_DTHREADS) {
-            const int i = e / NRB, q = e % NRB;
-            s_p[i][q] = i < nj ? X[(int64_t)(j0 + i) * NRB + q] : Sx::zero();
-        }
-        __syncthreads();
-        if (t < NRB) {
-            for (int j = nj - 1; j > 0; --j) {
-                const T yj = s_p[j][t];
-                for (int i = 0; i < j; i += SVB_CH) {
-                    T v[SVB_CH], l[SVB_CH];
-#pragma unroll
-                    for (int u = 0; u < SVB_CH; ++u) {
-                        v[u] = s_p[i + u][t];
-                        l[u] = s_t[j][i + u];
-                    }
-#pragma unroll
-                    for (int u = 0; u < SVB_CH; ++u)
-                        if (i + u < j) s_p[i + u][t] = Sx::fms(v[u], l[u], yj);
-                }
-            }
-        }
-        __syncthreads();
-        for (int e = t; e < nj * NRB; e += SVB_DTHREADS) X[(int64_t)j0 * NRB + e] = s_p[e / NRB][e % NRB];
-        for (int mf = wv; mf < j0 / 16; mf += NW) {
-            const int i = mf * 16 + lr; // < j0
-            typename M::acc_t acc[NF];
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf) acc[nf] = M::zero();
-            T a[SVP / KB][R];
-#pragma unroll
-            for (int b = 0; b < SVP / KB; ++b)
-                svb_krun<T, R>(L + i * ld + j0 + b * KB + lk * R, 0, nj - (b * KB + lk * R), conj, a[b]);
-#pragma unroll
-            for (int b = 0; b < SVP / KB; ++b)
-#pragma unroll
-                for (int jj = 0; jj < R; ++jj)
-#pragma unroll
-                    for (int nf = 0; nf < NF; ++nf)
-                        M::step(acc[nf], a[b][jj], s_p[b * KB + lk * R + jj][nf * 16 + lr]);
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                const int r = mf * 16 + M::row(lane, ii);
-#pragma unroll
-                for (int nf = 0; nf < NF; ++nf) {
-                    T *px = X + (int64_t)r * NRB + nf * 16 + lr;
-                    *px = Sx::sub(*px, M::get(acc[nf], ii));
-                }
-            }
-        }
-        __syncthreads();
-    }
+    svb_diag<T, true, true>(items, Lval, xb, conj);
 }
 
 // Forward push of U^T: X[gc_c, :] -= sum_i U(i, c) Z_k[i, :] for a chunk of
@@ -224,13 +131,12 @@ __global__ void __launch_bounds__(SV_THREADS)
 k_svb_utpanel(const SvChunk *chunks, const SvDiag *diag, const int64_t *coff, const int *ncol,
               const int64_t *ucol_voff, const int *ucol_fst, const int *ucol_gc, const T *Uval, T *xb,
               int conj) {
-    using Sx = S<T>;
     using M = Mma<T>;
     constexpr int NRB = SvbNr<T>::v, NF = NRB / 16, R = SvbRun<T>::v, KB = 4 * R;
     static_assert(SVU_COLS == 16 * (SV_THREADS / 64) && SVB_KS % KB == 0, "one fragment per wave, whole K blocks");
     const SvChunk ch = chunks[blockIdx.x];
     const SvDiag it = diag[ch.sn];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, lr = lane & 15, lk = lane >> 4;
+    const auto [t, lane, wv, lr, lk] = svb_lane();
     const int w = it.w;
     const int nc = min(SVU_COLS, ncol[ch.sn] - ch.c0);
     __shared__ int s_gc[SVU_COLS];
@@ -241,14 +147,10 @@ k_svb_utpanel(const SvChunk *chunks, const SvDiag *diag, const int64_t *coff, co
     const int rf = c < nc ? ucol_fst[e] - it.fst : w; // first row of the segment, relative; w: nothing to load
     const T *seg = Uval + (c < nc ? ucol_voff[e] : 0);
     typename M::acc_t acc[NF];
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf) acc[nf] = M::zero();
+    svb_acc_zero<T>(acc);
     for (int ks = 0; ks < w; ks += SVB_KS) {
         if (ks) __syncthreads();
-        for (int x = t; x < SVB_KS * NRB; x += SV_THREADS) {
-            const int k = x / NRB, q = x % NRB;
-            s_z[k][q] = ks + k < w ? xb[(int64_t)(it.fst + ks + k) * NRB + q] : Sx::zero();
-        }
+        svb_stage_rows<T, SVB_KS, SV_THREADS, false>(s_z, xb + (int64_t)(it.fst + ks) * NRB, w - ks, t);
         __syncthreads();
         if (wv * 16 < nc) {
             const int kend = min(SVB_KS, w - ks);
@@ -256,21 +158,14 @@ k_svb_utpanel(const SvChunk *chunks, const SvDiag *diag, const int64_t *coff, co
                 const int i0 = ks + kb + lk * R;
                 T a[R];
                 svb_krun<T, R>(seg + (i0 - rf), rf - i0, w - i0, conj, a);
-#pragma unroll
-                for (int jj = 0; jj < R; ++jj)
-#pragma unroll
-                    for (int nf = 0; nf < NF; ++nf) M::step(acc[nf], a[jj], s_z[kb + lk * R + jj][nf * 16 + lr]);
+                svb_krun_step<T>(acc, a, s_z, kb + lk * R, lr);
             }
         }
     }
 #pragma unroll
     for (int ii = 0; ii < 4; ++ii) {
         const int g = s_gc[wv * 16 + M::row(lane, ii)];
-        if (g >= 0) {
-            T *px = xb + (int64_t)g * NRB + lr;
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf) Sx::atomic_sub(px + nf * 16, M::get(acc[nf], ii));
-        }
+        if (g >= 0) svb_row_sub<T, true>(xb + (int64_t)g * NRB + lr, acc, ii);
     }
 }
 
@@ -287,32 +182,27 @@ template <typename T>
 __global__ void __launch_bounds__(SVB_LTHREADS)
 k_svb_ltpanel(const SvChunk *chunks, const SvDiag *pan, const int64_t *roff, const int *rows,
               const T *Lval, T *xb, int conj) {
-    using Sx = S<T>;
     using M = Mma<T>;
     constexpr int NRB = SvbNr<T>::v, NF = NRB / 16, R = SvbRun<T>::v, KB = 4 * R, NW = SVB_LTHREADS / 64;
     static_assert(SVB_KS % KB == 0, "whole K blocks");
     const SvChunk ch = chunks[blockIdx.x];
     const SvDiag it = pan[ch.sn];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, lr = lane & 15, lk = lane >> 4;
+    const auto [t, lane, wv, lr, lk] = svb_lane();
     const int w = it.w;
     const int nr = min(SV_THREADS, it.pad - ch.c0); // rows of this chunk
     const int64_t ld = it.ld;
     const T *L = Lval + it.voff + ch.c0; // L[r + j * ld] = L(chunk row r, column j)
     const int *grow = rows + roff[ch.sn] + ch.c0;
+    T *Y = xb + (int64_t)it.fst * NRB;
     __shared__ T s_x[SVB_KS][NRB];
     for (int m0 = 0; m0 < w; m0 += NW * 32) {
         const int jb = m0 + wv * 32;
         typename M::acc_t acc[2][NF];
-#pragma unroll
-        for (int mf = 0; mf < 2; ++mf)
-#pragma unroll
-            for (int nf = 0; nf < NF; ++nf) acc[mf][nf] = M::zero();
+        svb_acc_zero<T>(acc[0]);
+        svb_acc_zero<T>(acc[1]);
         for (int ks = 0; ks < nr; ks += SVB_KS) {
             __syncthreads();
-            for (int x = t; x < SVB_KS * NRB; x += SVB_LTHREADS) {
-                const int k = x / NRB, q = x % NRB;
-                s_x[k][q] = ks + k < nr ? xb[(int64_t)grow[ks + k] * NRB + q] : Sx::zero();
-            }
+            svb_stage_rows<T, SVB_KS, SVB_LTHREADS, true>(s_x, xb, nr - ks, t, grow + ks);
             __syncthreads();
             if (jb < w) {
                 const int kend = min(SVB_KS, nr - ks);
@@ -340,11 +230,7 @@ k_svb_ltpanel(const SvChunk *chunks, const SvDiag *pan, const int64_t *roff, con
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii) {
                 const int j = jb + mf * 16 + M::row(lane, ii);
-                if (j < w) {
-                    T *px = xb + (int64_t)(it.fst + j) * NRB + lr;
-#pragma unroll
-                    for (int nf = 0; nf < NF; ++nf) Sx::atomic_sub(px + nf * 16, M::get(acc[mf][nf], ii));
-                }
+                if (j < w) svb_row_sub<T, true>(Y + (int64_t)j * NRB + lr, acc[mf], ii);
             }
     }
 }
